@@ -25,6 +25,13 @@ Q-tables (168 GB per GPU, sized to HBM): replicas only, like configs[1].
 ``--workload config3`` (BASELINE.json configs[2]): 1M scenarios x 16 agents with battery storage
 over 8 GPUs = 125,000 scenarios (2M agents) per GPU, ONE shared f32 Q-table whose int64
 fixed-point TD deltas are all-reduced over RCCL once per episode (the path's real exchange step).
+
+A plain run (``--gpus 1 --steps K --warmup W``) sets up, warms up, times the K episodes and prints
+the result line.  ``--full`` adds what else the benchmark measures: the all-cores CPU baseline, the
+continuation through the reference's epsilon schedule (``value_at_eps``) and, after the default
+workload, configs[2], configs[4] and configs[3] on the same ranks (``secondary*``).
+``--dump-outputs DIR`` writes what the last timed episode computed as ``DIR/<name>.npy``; the
+inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -422,7 +429,7 @@ def cpu_baseline_dqn(seconds: float, S: int = 2, N: int = 2, R: int = 1, T: int 
                       f"episodes after one fill episode, oracle/dqn.py NumPy, {dt:.1f} s"}
 
 
-def run_dqn(args, rank, world, local, S, N, R, T, steps, warmup, cpu_seconds):
+def run_dqn(args, rank, world, local, S, N, R, T, steps, warmup, cpu_seconds, dump_dir=None):
     """configs[4]: DQN agents with ONE shared Q-network (data-parallel): every env step runs the
     act launch (greedy forwards on the Q-MLP, market, reward, replay append, RC update) and the
     train launch (32-sample batches on f32 MFMA) + gradient reduce (+ RCCL all-gather of the
@@ -497,6 +504,13 @@ def run_dqn(args, rank, world, local, S, N, R, T, steps, warmup, cpu_seconds):
     # every rank's replica of the shared network (the same Adam step on the same gathered sum)
     from p2pmicrogrid_amd.distributed import all_gather_concat
     fps = all_gather_concat(np.array([weights_fingerprint(eng.get_weights("online"))], np.uint64), world)
+    dumped = None
+    if dump_dir:  # the last timed episode's records, the networks and the state it left
+        arrays = {k: eng.get_record(k) for k in record}
+        arrays["episode_reward"] = eng.episode_reward()
+        arrays["t_in"], arrays["t_m"] = eng.get_temperatures()
+        arrays["weights_online"], arrays["weights_target"] = eng.get_weights("online"), eng.get_weights("target")
+        dumped = dump_outputs(dump_dir, rank, world, arrays)
     steps_per_episode = S * N * T
     flop = dqn_flop_per_agent_step(R)
     episode_ms = float(np.mean(kms)) if len(kms) else float("nan")
@@ -535,6 +549,8 @@ def run_dqn(args, rank, world, local, S, N, R, T, steps, warmup, cpu_seconds):
             out["collective"] = coll
         if os.environ.get("P2PMG_BENCH_TEST_DQN_ENGINE"):
             out["test_engine"] = os.environ["P2PMG_BENCH_TEST_DQN_ENGINE"]
+        if dumped:
+            out["dumped_outputs"] = dumped
     eng.close()
     if rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_seconds > 0:
         workers, rule = cpu_workers()
@@ -742,8 +758,65 @@ def timed(eng, world, fn):
     return max(rank_times), rank_times
 
 
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: what a rank writes stays under 64 MB, decimal or binary
+DUMP_SEED = 0
+
+
+def dump_sample(n: int, keep: int) -> np.ndarray:
+    """At most `keep` of range(n), sorted: the same seeded choice in every run (all when keep >= n)."""
+    if keep >= n:
+        return np.arange(n)
+    rs = np.random.RandomState(DUMP_SEED)
+    if n <= 1 << 24:
+        return np.sort(rs.permutation(n)[:keep])
+    return np.unique(rs.randint(0, n, size=keep))  # a year of records: no permutation of 10^9 indices
+
+
+def dump_outputs(dump_dir: str, rank: int, world: int, arrays: dict, tables=None) -> dict:
+    """--dump-outputs: what the timed path left after its last step, one ``<name>.npy`` per array
+    (``<name>.rank<r>.npy`` with several ranks), float32 or float64 as the path holds them.  The
+    budget (DUMP_BYTES) is split evenly over the files; an array above its share is written as a
+    fixed seeded sample of its flat elements, with the flat indices beside it in
+    ``<name>.index.npy``.  tables = (count, getter): whole Q-tables, a seeded choice of them that
+    fits what the arrays left of the budget (at least one share), fetched one by one
+    (``q_tables.npy`` + ``q_tables.index.npy``).  Returns the record that goes into the result line."""
+    os.makedirs(dump_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    share = DUMP_BYTES // (len(arrays) + (1 if tables else 0)) - 4096  # 4 KiB: headers and index files' slack
+    rec = {}
+    left = [DUMP_BYTES]
+
+    def save(name, a):
+        np.save(os.path.join(dump_dir, f"{name}{suffix}.npy"), a)
+        left[0] -= a.nbytes + 1024  # the .npy header is 128 bytes
+
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        keep = share // (a.itemsize + 8)  # a sampled element also costs its int64 index
+        if a.nbytes <= share:
+            save(name, a)
+            rec[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": False}
+        else:
+            idx = dump_sample(a.size, keep)
+            save(name, a.reshape(-1)[idx])
+            save(f"{name}.index", idx.astype(np.float64))
+            rec[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": int(idx.size)}
+    if tables:
+        count, get = tables
+        one = np.asarray(get(0))
+        idx = dump_sample(count, max(1, (left[0] - 8192) // (one.nbytes + 8)))
+        q = np.stack([one if k == 0 else np.asarray(get(int(k))) for k in idx])
+        q = q if q.dtype in (np.float32, np.float64) else q.astype(np.float64)
+        save("q_tables", q)
+        save("q_tables.index", idx.astype(np.float64))
+        rec["q_tables"] = {"shape": list(q.shape), "dtype": str(q.dtype), "tables": [int(k) for k in idx],
+                           "of": int(count)}
+    return {"dir": dump_dir, "files": rec}
+
+
 def run_tabular(args, rank, world, local, wl, *, S=None, N=None, R=None, T=None, q_dtype=None, steps=20,
-                warmup=5, cpu_seconds=10.0, schedule_to=0, eps_windows=(), window_steps=20):
+                warmup=5, cpu_seconds=10.0, schedule_to=0, eps_windows=(), window_steps=20, dump_dir=None):
     """One tabular workload (configs[1], [2] or [3]) on this rank: build the context, run `warmup`
     untimed then `steps` timed training episodes, and (rank 0) return its bench record; other ranks
     return None.  schedule_to > 0 (per-agent tables): the same context then continues the
@@ -894,6 +967,14 @@ def run_tabular(args, rank, world, local, wl, *, S=None, N=None, R=None, T=None,
     else:
         hashes = eng.table_hash_allgather() if shared else None  # every replica of the shared table
     steps_per_episode = S * N * T
+    dumped = None
+    if dump_dir:  # the last timed episode's records and the state it left, before anything else runs
+        arrays = {k: eng.get_record(k) for k in record}
+        arrays["episode_reward"] = eng.episode_reward()
+        arrays["t_in"], arrays["t_m"] = eng.get_temperatures()
+        if battery or hetero:
+            arrays["soc"] = eng.get_soc()
+        dumped = dump_outputs(dump_dir, rank, world, arrays, (eng.n_tables, lambda k: eng.get_q(k, 1)[0]))
 
     # the rest of the reference's schedule on the same context: epsilon windows + the whole continuation
     at_eps = None
@@ -1036,6 +1117,8 @@ def run_tabular(args, rank, world, local, wl, *, S=None, N=None, R=None, T=None,
             out["roofline"]["binding_frac"] = issue["frac"]
         if at_eps:
             out["value_at_eps"] = at_eps
+        if dumped:
+            out["dumped_outputs"] = dumped
     eng.close()
     if rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_seconds > 0:
         workers, rule = cpu_workers()
@@ -1074,8 +1157,8 @@ def main():
                     help="PMC summary for roofline.traffic (default profiles/pmc_traffic[_<workload>].json)")
     ap.add_argument("--schedule-episodes", type=int, default=None,
                     help="per-agent tables: continue the same context through the reference's epsilon schedule up "
-                         f"to this episode and time it (value_at_eps; default {REFERENCE_EPISODES} for config2, "
-                         "0 = off)")
+                         f"to this episode and time it (value_at_eps; default {REFERENCE_EPISODES} for config2 "
+                         "with --full, else 0 = off)")
     ap.add_argument("--eps-windows", default="500,960",
                     help="first episodes of the timed windows inside the schedule continuation")
     ap.add_argument("--eps-window-steps", type=int, default=20)
@@ -1090,8 +1173,8 @@ def main():
                     help="per-agent tables: chained launches (p2pmg_run_episodes, every wave running the "
                          "episodes up to the next metric point back to back) or one launch per episode")
     ap.add_argument("--secondary", default="auto", choices=["auto", "none", "config3"],
-                    help="a second workload measured by the same ranks after the first (auto: configs[2], the "
-                         "shared-table workload with the int64 delta all-reduce, after the default config2)")
+                    help="a second workload measured by the same ranks after the first (auto: with --full configs[2], "
+                         "the shared-table workload with the int64 delta all-reduce, after the default config2)")
     ap.add_argument("--secondary-scenarios", type=int, default=None)
     ap.add_argument("--secondary-agents", type=int, default=None)
     ap.add_argument("--secondary-horizon", type=int, default=None)
@@ -1099,16 +1182,27 @@ def main():
     ap.add_argument("--secondary-warmup", type=int, default=2)
     ap.add_argument("--secondary-cpu-seconds", type=float, default=5.0)
     ap.add_argument("--extra", default="auto",
-                    help="further workloads measured by the same ranks after the secondary, comma-separated (auto: "
-                         "config5,config4 = configs[4] DQN and configs[3] one-year mixes after the default config2; "
+                    help="further workloads measured by the same ranks after the secondary, comma-separated (auto: with "
+                         "--full config5,config4 = configs[4] DQN and configs[3] one-year mixes after the default config2; "
                          "'' = none)")
     ap.add_argument("--extra-scenarios", type=int, default=None, help="override the extras' scenarios per GPU")
     ap.add_argument("--extra-horizon", type=int, default=None, help="override the extras' horizon")
     ap.add_argument("--extra-steps", type=int, default=5)
     ap.add_argument("--extra-warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the all-cores CPU baseline, the epsilon-schedule "
+                         "continuation (value_at_eps) and the secondary / extra workloads.  Without it "
+                         "--schedule-episodes, --secondary and --extra default to off and no CPU baseline runs: "
+                         "set-up, warm-up, the timed steps, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (records, episode rewards, "
+                         "temperatures, Q-tables or networks; at most 64 MB, seeded samples above that) as "
+                         "DIR/<name>.npy; --workload's run only")
     args = ap.parse_args()
     if args.gpus is not None and args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if not args.full:
+        args.no_cpu_baseline = True
     if "WORLD_SIZE" not in os.environ:
         args.gpus = args.gpus or 1
         if args.gpus > 1:
@@ -1120,7 +1214,7 @@ def main():
         S, N, R, T, _, _, _ = WORKLOADS["config5"]
         R = R if args.rounds is None else args.rounds
         out = run_dqn(args, rank, world, local, args.scenarios or S, args.agents or N, R, args.horizon or T,
-                      args.steps, args.warmup, args.cpu_seconds)
+                      args.steps, args.warmup, args.cpu_seconds, dump_dir=args.dump_outputs)
         if rank == 0:
             print(json.dumps(out), flush=True)
         if world > 1:
@@ -1129,15 +1223,15 @@ def main():
         return 0
     sched = args.schedule_episodes
     if sched is None:
-        sched = REFERENCE_EPISODES if args.workload == "config2" else 0
+        sched = REFERENCE_EPISODES if args.full and args.workload == "config2" else 0
     windows = [int(x) for x in args.eps_windows.split(",") if x.strip()]
     out = run_tabular(args, rank, world, local, args.workload, S=args.scenarios, N=args.agents, R=args.rounds,
                       T=args.horizon, q_dtype=args.q_dtype, steps=args.steps, warmup=args.warmup,
                       cpu_seconds=args.cpu_seconds, schedule_to=sched, eps_windows=windows,
-                      window_steps=args.eps_window_steps)
+                      window_steps=args.eps_window_steps, dump_dir=args.dump_outputs)
     sec_wl = args.secondary
     if sec_wl == "auto":
-        sec_wl = "config3" if args.workload == "config2" else "none"
+        sec_wl = "config3" if args.full and args.workload == "config2" else "none"
     if sec_wl != "none" and sec_wl != args.workload:
         # SURVEY §8d judges the roofline on configs[2]; at world > 1 its per-episode int64 delta
         # all-reduce is the path's real exchange over xGMI, so the driver's scaling runs carry it too
@@ -1158,7 +1252,7 @@ def main():
     # and configs[3] (one-year heterogeneous episodes)
     extra = args.extra
     if extra == "auto":
-        extra = "config5,config4" if args.workload == "config2" else ""
+        extra = "config5,config4" if args.full and args.workload == "config2" else ""
     for wl in [x.strip() for x in extra.split(",") if x.strip() and x.strip() != args.workload]:
         key = {"config5": "secondary_dqn", "config4": "secondary_year"}.get(wl, f"secondary_{wl}")
         try:

@@ -8,7 +8,7 @@ O="$R/gpurun_out/ab_default"; mkdir -p "$O"
 for i in $(seq 1 "$REPS"); do
   for L in "$@"; do
     n=$(basename "$L" .so)
-    P2PMG_LIB="$R/$L" timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --secondary none \
+    P2PMG_LIB="$R/$L" timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --secondary none \
       > "$O/${n}_$i.json" 2> "$O/${n}_$i.err" || { tail -20 "$O/${n}_$i.err"; exit 1; }
     python -c "
 import json; d=json.loads(open('$O/${n}_$i.json').read().splitlines()[-1])

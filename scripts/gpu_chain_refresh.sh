@@ -8,7 +8,7 @@ O="$R/gpurun_out/$RND"; mkdir -p "$O"
 PO="--secondary none --schedule-episodes 0"
 run() {  # name timeout args...
   local n=$1 to=$2; shift 2
-  timeout -k 10 "$to" python -u bench.py "$@" > "$O/$n.json" 2> "$O/$n.err" || { tail -20 "$O/$n.err"; exit 1; }
+  timeout -k 10 "$to" python -u bench.py --full "$@" > "$O/$n.json" 2> "$O/$n.err" || { tail -20 "$O/$n.err"; exit 1; }
   tail -c 300 "$O/$n.json"; echo
 }
 run c2 400 --gpus 1 --steps 20 --warmup 5
@@ -16,5 +16,5 @@ run c2off 300 --steps 20 --warmup 5 --no-cpu-baseline $PO --chain off
 run c2long 300 --steps 200 --warmup 10 --no-cpu-baseline $PO
 run c2n2 400 --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/prof_c2" -o c2 --output-format csv -- python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$O/prof_c2.json" 2> "$O/prof_c2.log" || { tail -20 "$O/prof_c2.log"; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/prof_c2" -o c2 --output-format csv -- python3 "$R/bench.py" --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$O/prof_c2.json" 2> "$O/prof_c2.log" || { tail -20 "$O/prof_c2.log"; exit 1; }
 echo done

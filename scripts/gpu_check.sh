@@ -10,6 +10,6 @@ if [ -n "$2" ]; then
 fi
 for W in $3; do
   ST=50; [ "$W" = config3 ] && ST=10; [ "$W" = config4 ] && ST=2; [ "$W" = config5 ] && ST=5
-  timeout -k 10 400 python -u bench.py --workload "$W" --steps $ST --warmup 2 --no-cpu-baseline --secondary none --schedule-episodes 0 > "$O/bench_$W.json" 2> "$O/bench_$W.err" || { tail -20 "$O/bench_$W.err"; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --workload "$W" --steps $ST --warmup 2 --no-cpu-baseline --secondary none --schedule-episodes 0 > "$O/bench_$W.json" 2> "$O/bench_$W.err" || { tail -20 "$O/bench_$W.err"; exit 1; }
   python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['value'], d['roofline']['kernel_ms'], d['roofline'].get('kernel'))" "$O/bench_$W.json" "$W"
 done

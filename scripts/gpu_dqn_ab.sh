@@ -8,7 +8,7 @@ bash scripts/gpu_ab.sh config5 1 $1 || exit 1
 cd /tmp && export TMPDIR=/tmp
 for L in $1; do
   n=$(basename "$L" .so)
-  P2PMG_LIB="$R/$L" timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof_$n" -o "$n" --output-format csv -- python3 "$R/bench.py" --workload config5 --steps 3 --warmup 1 --no-cpu-baseline > "$O/prof_$n.log" 2>&1 || { tail -20 "$O/prof_$n.log"; exit 1; }
+  P2PMG_LIB="$R/$L" timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof_$n" -o "$n" --output-format csv -- python3 "$R/bench.py" --full --workload config5 --steps 3 --warmup 1 --no-cpu-baseline > "$O/prof_$n.log" 2>&1 || { tail -20 "$O/prof_$n.log"; exit 1; }
   f=$(find "$O/prof_$n" -name "*kernel_stats.csv" | head -1)
   echo "== $n"; cut -d, -f1-4 "$f" | head -5
 done

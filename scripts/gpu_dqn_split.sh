@@ -26,12 +26,12 @@ setform() {
 }
 for V in $FORMS; do
   setform $V
-  timeout -k 10 300 python -u bench.py --workload config5 --steps 10 --warmup 2 --no-cpu-baseline $A > "$O/bench_$V.json" 2> "$O/bench_$V.err" || { tail -20 "$O/bench_$V.err"; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --workload config5 --steps 10 --warmup 2 --no-cpu-baseline $A > "$O/bench_$V.json" 2> "$O/bench_$V.err" || { tail -20 "$O/bench_$V.err"; exit 1; }
   tail -c 300 "$O/bench_$V.json"; echo
 done
 cd /tmp && export TMPDIR=/tmp
 for V in $FORMS; do
   setform $V
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof_$V" -o "$V" --output-format csv -- python3 "$R/bench.py" --workload config5 --steps 3 --warmup 1 --no-cpu-baseline $A > "$O/prof_$V.log" 2>&1 || { tail -20 "$O/prof_$V.log"; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof_$V" -o "$V" --output-format csv -- python3 "$R/bench.py" --full --workload config5 --steps 3 --warmup 1 --no-cpu-baseline $A > "$O/prof_$V.log" 2>&1 || { tail -20 "$O/prof_$V.log"; exit 1; }
 done
 echo done

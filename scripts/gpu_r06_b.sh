@@ -6,5 +6,5 @@ timeout -k 10 1000 python -u -m pytest -x -v -s --timeout 1050 --timeout-method 
   > "$O/config4_full.txt" 2>&1 || { tail -30 "$O/config4_full.txt"; exit 1; }
 tail -3 "$O/config4_full.txt"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/prof_default" -o p --output-format csv -- python "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$O/prof_default.json" 2> "$O/prof_default.err" || { tail -20 "$O/prof_default.err"; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/prof_default" -o p --output-format csv -- python "$R/bench.py" --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$O/prof_default.json" 2> "$O/prof_default.err" || { tail -20 "$O/prof_default.err"; exit 1; }
 find "$O/prof_default" -name "*kernel_stats.csv"

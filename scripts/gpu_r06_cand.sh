@@ -10,7 +10,7 @@ tail -2 "$O/tests.txt"
 for i in 1 2 3; do
   for V in base head; do
     if [ $V = base ]; then export P2PMG_LIB="$R/build/libp2pmg_base.so"; else unset P2PMG_LIB; fi
-    timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --secondary none --extra "" --no-cpu-baseline \
+    timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --secondary none --extra "" --no-cpu-baseline \
       --schedule-episodes 0 > "$O/bench_${V}_$i.json" 2> "$O/bench_${V}_$i.err" || { tail -20 "$O/bench_${V}_$i.err"; exit 1; }
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['value'], d['roofline']['kernel_ms_per_launch'])" "$O/bench_${V}_$i.json" "$V $i"
   done

@@ -11,7 +11,7 @@ timeout -k 10 300 python -u -m pytest -x -v -s --timeout 240 --timeout-method th
   > "$O/f32_mode.txt" 2>&1 || { tail -30 "$O/f32_mode.txt"; exit 1; }
 grep "max relative" "$O/f32_mode.txt"
 t0=$(date +%s.%N)
-timeout -k 10 560 python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_default.json" 2> "$O/bench_default.err" || { tail -30 "$O/bench_default.err"; exit 1; }
+timeout -k 10 560 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_default.json" 2> "$O/bench_default.err" || { tail -30 "$O/bench_default.err"; exit 1; }
 t1=$(date +%s.%N)
 echo "bench wall_s $(python -c "print($t1 - $t0)")" | tee "$O/bench_default.wall"
 python - "$O/bench_default.json" <<'PY'

@@ -13,7 +13,7 @@ O="$R/gpurun_out/$RND"; mkdir -p "$O"
 PART="${2:-A}"
 run() {  # name timeout args...
   local n=$1 to=$2; shift 2
-  timeout -k 10 "$to" python -u bench.py "$@" > "$O/$n.json" 2> "$O/$n.err" || { tail -20 "$O/$n.err"; exit 1; }
+  timeout -k 10 "$to" python -u bench.py --full "$@" > "$O/$n.json" 2> "$O/$n.err" || { tail -20 "$O/$n.err"; exit 1; }
   tail -c 300 "$O/$n.json"; echo
 }
 if [ "$PART" = A ]; then
@@ -28,11 +28,11 @@ fi
 cd /tmp && export TMPDIR=/tmp
 prof() {  # name timeout args...
   local n=$1 to=$2; shift 2
-  timeout -k 10 "$to" rocprofv3 --kernel-trace --stats -d "$O/prof_$n" -o "$n" --output-format csv -- python3 "$R/bench.py" "$@" --no-cpu-baseline > "$O/prof_$n.log" 2>&1 || { tail -20 "$O/prof_$n.log"; exit 1; }
+  timeout -k 10 "$to" rocprofv3 --kernel-trace --stats -d "$O/prof_$n" -o "$n" --output-format csv -- python3 "$R/bench.py" --full "$@" --no-cpu-baseline > "$O/prof_$n.log" 2>&1 || { tail -20 "$O/prof_$n.log"; exit 1; }
 }
 pmc() {  # name counters timeout args...
   local n=$1 c=$2 to=$3; shift 3
-  timeout -s KILL "$to" rocprofv3 --pmc $c --kernel-trace -d "$O/pmc_${n}_${c%% *}" -o "${c%% *}" --output-format csv -- python3 "$R/bench.py" "$@" --no-cpu-baseline > "$O/pmc_${n}_${c%% *}.log" 2>&1 || { tail -20 "$O/pmc_${n}_${c%% *}.log"; exit 1; }
+  timeout -s KILL "$to" rocprofv3 --pmc $c --kernel-trace -d "$O/pmc_${n}_${c%% *}" -o "${c%% *}" --output-format csv -- python3 "$R/bench.py" --full "$@" --no-cpu-baseline > "$O/pmc_${n}_${c%% *}.log" 2>&1 || { tail -20 "$O/pmc_${n}_${c%% *}.log"; exit 1; }
 }
 if [ "$PART" = A ]; then
 prof c2 400 --gpus 1 --steps 20 --warmup 5
@@ -56,11 +56,11 @@ for W in config2 config3; do
   ST=8; [ $W = config3 ] && ST=2
   for P in A B; do
     C=$PA; [ $P = B ] && C=$PB
-    timeout -s KILL 240 rocprofv3 --pmc $C --kernel-trace -d "$O/sq/${W}_$P" -o p --output-format csv -- python3 "$R/bench.py" --workload $W --steps $ST --warmup 1 --no-cpu-baseline $PO > "$O/sq_${W}_$P.log" 2>&1 || { tail -20 "$O/sq_${W}_$P.log"; exit 1; }
+    timeout -s KILL 240 rocprofv3 --pmc $C --kernel-trace -d "$O/sq/${W}_$P" -o p --output-format csv -- python3 "$R/bench.py" --full --workload $W --steps $ST --warmup 1 --no-cpu-baseline $PO > "$O/sq_${W}_$P.log" 2>&1 || { tail -20 "$O/sq_${W}_$P.log"; exit 1; }
   done
 done
 # configs[4]: the DQN kernels' MFMA busy cycles beside the clock (SQ_BUSY_CYCLES) and the VALU / LDS
 # issue that shares the SIMDs with the MFMA stream
 PC="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU"
-timeout -s KILL 240 rocprofv3 --pmc $PC --kernel-trace -d "$O/sq/config5_C" -o p --output-format csv -- python3 "$R/bench.py" --workload config5 --steps 2 --warmup 1 --no-cpu-baseline > "$O/sq_config5_C.log" 2>&1 || { tail -20 "$O/sq_config5_C.log"; exit 1; }
+timeout -s KILL 240 rocprofv3 --pmc $PC --kernel-trace -d "$O/sq/config5_C" -o p --output-format csv -- python3 "$R/bench.py" --full --workload config5 --steps 2 --warmup 1 --no-cpu-baseline > "$O/sq_config5_C.log" 2>&1 || { tail -20 "$O/sq_config5_C.log"; exit 1; }
 echo done

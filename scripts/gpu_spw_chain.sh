@@ -6,7 +6,7 @@ REPS="$1"; SPWS="$2"
 O="$R/gpurun_out/spw_chain"; mkdir -p "$O"
 for i in $(seq 1 "$REPS"); do
   for W in $SPWS; do
-    P2PMG_SPW=$W timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --secondary none $EXTRA \
+    P2PMG_SPW=$W timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --secondary none $EXTRA \
       > "$O/spw${W}_$i.json" 2> "$O/spw${W}_$i.err" || { tail -20 "$O/spw${W}_$i.err"; exit 1; }
     python -c "
 import json; d=json.loads(open('$O/spw${W}_$i.json').read().splitlines()[-1])

@@ -11,8 +11,8 @@ PB="SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_SMEM S
 cd /tmp && export TMPDIR=/tmp
 for P in A B; do
   C=$PA; [ $P = B ] && C=$PB
-  P2PMG_NO_SPEC=1 timeout -s KILL 240 rocprofv3 --pmc $C --kernel-trace -d "$O/sq/config3_$P" -o p --output-format csv -- python3 "$R/bench.py" --workload config3 --steps 2 --warmup 1 --no-cpu-baseline $PO > "$O/sq_config3_$P.log" 2>&1 || { tail -20 "$O/sq_config3_$P.log"; exit 1; }
+  P2PMG_NO_SPEC=1 timeout -s KILL 240 rocprofv3 --pmc $C --kernel-trace -d "$O/sq/config3_$P" -o p --output-format csv -- python3 "$R/bench.py" --full --workload config3 --steps 2 --warmup 1 --no-cpu-baseline $PO > "$O/sq_config3_$P.log" 2>&1 || { tail -20 "$O/sq_config3_$P.log"; exit 1; }
 done
 cd "$R"
-timeout -k 10 400 python -u bench.py --workload config3 --steps 10 --warmup 2 > "$O/c3.json" 2> "$O/c3.err" || { tail -20 "$O/c3.err"; exit 1; }
+timeout -k 10 400 python -u bench.py --full --workload config3 --steps 10 --warmup 2 > "$O/c3.json" 2> "$O/c3.err" || { tail -20 "$O/c3.err"; exit 1; }
 echo done

@@ -9,7 +9,7 @@ if [ "$WHAT" = all ] || [ "$WHAT" = tests ]; then
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > "$O/pytest.log" 2>&1 || { tail -40 "$O/pytest.log"; exit 1; }
 tail -3 "$O/pytest.log"
 fi
-timeout -k 10 300 python -u bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 300 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 cat "$O/bench.json"
 cd /tmp && export TMPDIR=/tmp
 PA="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU"
@@ -19,7 +19,7 @@ for W in config2 config3; do
   ST=8; [ $W = config3 ] && ST=2
   for P in A B; do
     C=$PA; [ $P = B ] && C=$PB
-    timeout -s KILL 240 rocprofv3 --pmc $C --kernel-trace -d "$O/${W}_$P" -o p --output-format csv -- python3 "$R/bench.py" --workload $W --steps $ST --warmup 1 --no-cpu-baseline > "$O/${W}_$P.log" 2>&1 || { tail -20 "$O/${W}_$P.log"; exit 1; }
+    timeout -s KILL 240 rocprofv3 --pmc $C --kernel-trace -d "$O/${W}_$P" -o p --output-format csv -- python3 "$R/bench.py" --full --workload $W --steps $ST --warmup 1 --no-cpu-baseline > "$O/${W}_$P.log" 2>&1 || { tail -20 "$O/${W}_$P.log"; exit 1; }
   done
 done
 mkdir -p "$O/sq" && python3 "$R/scripts/summarize_sq.py" "$O" "$O/sq" > "$O/sq_summary.json" && cat "$O/sq_summary.json"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-phase kernel durations of the driver's default bench command from its rocprofv3 kernel trace.
 
-The default command (``bench.py --gpus 1 --steps 20 --warmup 5``) launches episode_fast_kernel for
+That command (``bench.py --full --gpus 1 --steps 20 --warmup 5``) launches episode_fast_kernel for
 the configs[1] warm-up (episodes 0-4), the timed region (5-24) and the epsilon-schedule
 continuation (25-999, value_at_eps), then episode_sq16_kernel for the configs[2] secondary
 (2 warm-up + 10 timed).  rocprofv3 --stats averages over every launch, so its configs[1] average

@@ -88,6 +88,16 @@ class OracleEngine:
         q = self.ob.q
         return q[first:first + (len(q) - first if count is None else count)].copy()
 
+    @property
+    def n_tables(self):
+        return len(self.ob.q)
+
+    def get_record(self, name):
+        return np.asarray(self.last[name])
+
+    def get_temperatures(self):
+        return self.ob.t_in.copy(), self.ob.t_m.copy()
+
 
 class OracleDQNEngine(OracleEngine):
     """DeviceDQNBatch's interface (one shared network) computed by oracle/dqn.py, with the same

@@ -1,7 +1,11 @@
 """world_size-2 gloo runs of the sharded trainer on CPU (oracle-backed stand-in engine):
 sharding + metric collectives reproduce the single-process result scenario for scenario."""
+import importlib.util
+import json
 import os
 import socket
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -335,7 +339,7 @@ def test_bench_host_rehearsal_dqn():
     assert d["exchange"] == "host-rehearsal" and d["network_replicas_identical"] and d["n_gpus"] == 2
 
 
-SMALL_DEFAULT_LINE = ("--steps", "2", "--warmup", "1", "--horizon", "12", "--schedule-episodes", "24",
+SMALL_DEFAULT_LINE = ("--full", "--steps", "2", "--warmup", "1", "--horizon", "12", "--schedule-episodes", "24",
                       "--eps-windows", "6,15", "--eps-window-steps", "3", "--secondary-agents", "4",
                       "--secondary-horizon", "12", "--secondary-steps", "2", "--secondary-warmup", "1",
                       "--extra-horizon", "12", "--extra-steps", "2", "--extra-warmup", "1")
@@ -370,7 +374,7 @@ def default_line_world1():
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("world", [1, 2, 8])
 def test_bench_default_line_carries_configs2_secondary_and_value_at_eps(world, default_line_world1):
-    """The driver's default command: the configs[1] line, then configs[2] (shared table, int64 delta
+    """The default command with ``--full``: the configs[1] line, then configs[2] (shared table, int64 delta
     exchange) measured by the same ranks as ``secondary``, and configs[1] continued through the
     reference's epsilon schedule as ``value_at_eps``.  World 1, 2 and 8 (the driver's SCALE points)
     process the same global scenarios (8 per job), so every mean reward equals world 1's."""
@@ -418,6 +422,86 @@ def test_bench_default_line_carries_configs2_secondary_and_value_at_eps(world, d
     assert d["mean_episode_reward"] == pytest.approx(w1["mean_episode_reward"], rel=1e-12)
     assert ve["mean_episode_reward_last"] == pytest.approx(w1["value_at_eps"]["mean_episode_reward_last"], rel=1e-12)
     assert s["mean_episode_reward"] == pytest.approx(w1["secondary"]["mean_episode_reward"], rel=1e-12)
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without ``--full`` the line is the configs[1] measurement alone (no CPU baseline, schedule
+    continuation, secondary or extra workloads) with --steps timed episodes; ``--dump-outputs``
+    writes the last timed episode's arrays as float .npy files within 64 MB, identical from run to
+    run, and equal to the oracle's own arrays."""
+    root, env = _bench_env()
+    common = ("--gpus", "1", "--steps", "3", "--warmup", "1", "--scenarios", "5", "--horizon", "12")
+    cmd = [sys.executable, os.path.join(root, "bench.py"), *common, "--dump-outputs", str(tmp_path / "a")]
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][0])
+    for k in ("cpu_baseline", "value_at_eps", "secondary", "secondary_dqn", "secondary_year"):
+        assert k not in d
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert sum(n for _, n in d["launch"]["launches"]) == 4  # warm-up + timed episodes, nothing after them
+    assert d["value"] == pytest.approx(5 * 2 * 12 / (d["ms_per_step"] * 1e-3))
+    d2 = _bench_line(root, env, *common, "--dump-outputs", str(tmp_path / "b"))
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == sorted(f.name for f in (tmp_path / "b").iterdir())
+    assert {"reward.npy", "cost.npy", "episode_reward.npy", "t_in.npy", "t_m.npy", "q_tables.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += (tmp_path / "a" / n).stat().st_size
+    assert total <= 64 * 2 ** 20
+    assert np.load(tmp_path / "a" / "reward.npy").shape == (12, 5, 2)
+    qrec = d2["dumped_outputs"]["files"]["q_tables"]  # 10 f64 tables of 3.84 MB fit beside the small arrays
+    assert qrec["of"] == 10 and qrec["tables"] == list(range(10))
+    assert np.array_equal(np.load(tmp_path / "a" / "q_tables.index.npy"), qrec["tables"])
+    # the same four episodes by the oracle engine directly
+    from bench_test_engine import BenchOracleEngine
+    from p2pmicrogrid_amd.dataset import scenario_batch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    inp = scenario_batch(5, 2, 12)
+    e = BenchOracleEngine(5, 2, 1, 12)
+    e.set_env(np.broadcast_to(inp.time, inp.t_out.shape), inp.t_out)
+    e.set_profiles(inp.load_w, inp.pv_w)
+    e.set_max_in(inp.max_in)
+    e.set_temperatures(inp.t_in0, inp.t_m0)
+    e.run_episodes(0, [bench.epsilon_at(k) for k in range(4)], reset_sigma=0.3)
+    assert np.array_equal(np.load(tmp_path / "a" / "reward.npy"), e.get_record("reward"))
+    assert np.array_equal(np.load(tmp_path / "a" / "q_tables.npy"), e.get_q()[qrec["tables"]])
+    assert np.array_equal(np.load(tmp_path / "a" / "t_in.npy"), e.get_temperatures()[0])
+
+
+def test_bench_dump_samples_an_output_above_its_share(tmp_path):
+    """An array above its share of the 64 MB is written as a fixed seeded sample of its flat
+    elements with their indices; whole Q-tables are a seeded choice that fits the share."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = np.arange(20_000_000, dtype=np.float32)  # 80 MB
+    small = np.arange(7, dtype=np.int32)
+    tables = np.arange(40 * 1_000_000, dtype=np.float64).reshape(40, 1_000_000)  # 8 MB each
+    fetched = []
+
+    def get(k):
+        fetched.append(k)
+        return tables[k]
+
+    rec = bench.dump_outputs(str(tmp_path), 0, 1, {"big": big, "small": small}, (40, get))
+    files = {f.name: f.stat().st_size for f in tmp_path.iterdir()}
+    assert sum(files.values()) <= 64 * 2 ** 20
+    idx = np.load(tmp_path / "big.index.npy").astype(np.int64)
+    assert 1_000_000 < idx.size == rec["files"]["big"]["sampled"] and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "big.npy"), big[idx])
+    assert np.load(tmp_path / "small.npy").dtype == np.float64
+    tq = np.load(tmp_path / "q_tables.index.npy").astype(np.int64)
+    assert 2 <= tq.size < 40 and np.array_equal(np.load(tmp_path / "q_tables.npy"), tables[tq])
+    assert sorted(set(fetched)) == sorted({0, *tq})  # only the chosen tables (and table 0 for the size) are fetched
+    bench.dump_outputs(str(tmp_path / "again"), 0, 1, {"big": big, "small": small}, (40, get))
+    for n in ("big.index.npy", "q_tables.index.npy"):  # the same choice every time
+        assert np.array_equal(np.load(tmp_path / "again" / n), np.load(tmp_path / n))
 
 
 def test_visible_gpus_without_runtime(monkeypatch):
