@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define P2PMG_ABI_VERSION 8  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL */
+#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels */
 
 typedef struct p2pmg_ctx p2pmg_ctx;
 
@@ -142,8 +142,8 @@ typedef struct p2pmg_episode_args {
 #define P2PMG_FLAG_PHILOX_PREPASS 1
 #define P2PMG_FLAG_PHILOX_INKERNEL 2
 /* Kernel choice.  Automatic: the fast per-agent-table kernel (step pre-pass + rounds unrolled at
- * compile time) whenever it applies (N <= 8, R + 1 <= 4, no battery, no shared table, in-range
- * max_in); GENERAL forces the general episode kernel (same results, bit for bit). */
+ * compile time) whenever it applies (N <= 8, R + 1 <= 4, or R + 1 <= 2 with a battery, no shared
+ * table, in-range max_in); GENERAL forces the general episode kernel (same results, bit for bit). */
 #define P2PMG_FLAG_GENERAL_KERNEL 4
 /* End the episode with HPHeating.reset (community.py:181 -> heating.py:145-152): T0 for episode + 1
  * drawn as p2pmg_reset_temperatures_philox(ctx, episode + 1, reset_sigma) would, fused into the
@@ -178,7 +178,7 @@ int p2pmg_set_profiles(p2pmg_ctx* ctx, const float* load_w, const float* pv_w); 
 int p2pmg_set_agent_params(p2pmg_ctx* ctx, const float* max_in);              /* [A] */
 int p2pmg_set_temperatures(p2pmg_ctx* ctx, const float* t_in, const float* t_m); /* [A] */
 int p2pmg_get_temperatures(p2pmg_ctx* ctx, float* t_in, float* t_m);
-int p2pmg_reset_temperatures_philox(p2pmg_ctx* ctx, int episode, double sigma); /* T0 ~ N(setpoint, sigma) */
+int p2pmg_reset_temperatures_philox(p2pmg_ctx* ctx, int episode, double sigma); /* T0 ~ N(setpoint of the agent, sigma) */
 int p2pmg_set_replay_codes(p2pmg_ctx* ctx, const uint8_t* codes);            /* [T][R+1][A] */
 
 /* Q-tables in the reference layout (n_time, n_temp, n_bal, n_p2p, n_actions) per agent */
@@ -232,6 +232,9 @@ int p2pmg_set_timing_period(p2pmg_ctx* ctx, int period);
 /* batched primitives (device) for unit parity against the reference functions */
 int p2pmg_rc_step(p2pmg_ctx* ctx, int n, const float* t_out, const float* t_in, const float* t_m,
                   const float* hp, float* t_in_new, float* t_m_new);
+/* p2pmg_rc_step with per-element COP (NULL = config) and solar_gain = f32(gA * solar_rad) */
+int p2pmg_rc_step_ex(p2pmg_ctx* ctx, int n, const float* t_out, const float* t_in, const float* t_m,
+                     const float* hp, const float* cop, float solar_gain, float* t_in_new, float* t_m_new);
 int p2pmg_state_indices(p2pmg_ctx* ctx, int n, const float* obs /* [n][4] */, int32_t* idx /* [n][4] */);
 /* The kernels' fast divisions next to the IEEE operator, for the division fuzz test (the quotients
  * the reference takes in agent.py:175,193,203, community.py:63 and storage.py:58,61,64).
@@ -242,6 +245,16 @@ int p2pmg_fdiv64_check(p2pmg_ctx* ctx, int n, const double* a, const double* b, 
 
 /* heterogeneous agents and storage (configs 3-4) */
 int p2pmg_set_hp_levels(p2pmg_ctx* ctx, const float* levels /* [A][3] W per action */);
+int p2pmg_get_hp_levels(p2pmg_ctx* ctx, float* levels /* [A][3] */);
+/* per-agent comfort and heat pump (HPHeating / HeatPump, heating.py:92-130): [A][4] =
+ * {setpoint, lower_bound, upper_bound, cop}; NULL restores the config's values.  The bounds are the
+ * caller's: the reference forms setpoint -/+ 1.0 in f64 and casts to f32 afterwards, which differs
+ * from an f32 subtraction for a setpoint such as 21.3.  Non-finite values and lower > upper:
+ * P2PMG_E_INVALID.  Every episode kernel reads these (rule, tabular, DQN), as do the T0 draws; a
+ * shared-table N = 16 context with values set here runs the general kernel's shared-table form
+ * instead of episode_sq16_kernel (same results, bit for bit) until NULL restores the config's. */
+int p2pmg_set_thermal(p2pmg_ctx* ctx, const float* params);
+int p2pmg_get_thermal(p2pmg_ctx* ctx, float* params);
 /* Battery per agent (storage.py:36-76, rule agent.py:138-153, f64): capacity [A] in J (0 = none;
  * NULL disables storage), SoC bounds, round-trip efficiency, initial SoC [A] (NULL = 0.5). */
 int p2pmg_set_battery(p2pmg_ctx* ctx, const double* capacity, double min_soc, double max_soc,

@@ -41,6 +41,7 @@ EXPORTS = [
     "p2pmg_dqn_get_net_steps", "p2pmg_fdiv_check", "p2pmg_fdiv64_check", "p2pmg_comm_nranks",
     "p2pmg_allreduce_metrics", "p2pmg_table_hash_allgather", "p2pmg_dqn_set_exchange", "p2pmg_dqn_grad_layout",
     "p2pmg_run_episodes", "p2pmg_get_episode_rewards",
+    "p2pmg_set_thermal", "p2pmg_get_thermal", "p2pmg_rc_step_ex", "p2pmg_get_hp_levels",
 ]
 
 
@@ -65,7 +66,7 @@ class DqnConfig(C.Structure):
                 ("capacity", C.c_int32), ("agents_per_block", C.c_int32), ("grad_segments", C.c_int32)]
 
 
-ABI_VERSION = 8  # include/p2pmg.h P2PMG_ABI_VERSION
+ABI_VERSION = 9  # include/p2pmg.h P2PMG_ABI_VERSION
 
 # p2pmg_exchange_fn: int (*)(void* user, float* segments, int64_t floats_per_rank, int rank, int nranks)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int, C.c_int)
@@ -120,6 +121,7 @@ def _declare(lib):
         "p2pmg_get_episode_reward": ([vp, fp], i32),
         "p2pmg_last_kernel_ms": ([vp, C.POINTER(C.c_float)], i32),
         "p2pmg_rc_step": ([vp, i32, fp, fp, fp, fp, fp, fp], i32),
+        "p2pmg_rc_step_ex": ([vp, i32, fp, fp, fp, fp, vp, C.c_float, fp, fp], i32),
         "p2pmg_state_indices": ([vp, i32, fp, vp], i32),
         "p2pmg_replay_decode": ([vp, sz, sz, vp, sz, vp, C.POINTER(sz)], i32),
         "p2pmg_device_count": ([C.POINTER(C.c_int)], i32),
@@ -129,6 +131,9 @@ def _declare(lib):
         "p2pmg_set_timing_period": ([vp, i32], i32),
         "p2pmg_q_calls": ([vp, i32, vp, vp, vp, vp, vp, i32, vp, vp], i32),
         "p2pmg_set_hp_levels": ([vp, fp], i32),
+        "p2pmg_get_hp_levels": ([vp, fp], i32),
+        "p2pmg_set_thermal": ([vp, vp], i32),
+        "p2pmg_get_thermal": ([vp, fp], i32),
         "p2pmg_run_rule_episode": ([vp, i32], i32),
         "p2pmg_set_hp_state": ([vp, fp], i32),
         "p2pmg_get_hp_state": ([vp, fp], i32),

@@ -29,6 +29,21 @@ from .rng import ReferenceRNG, dqn_episode_draws, python_random
 from .storage import BatteryStorage, NoStorage
 
 F32 = np.float32
+ACTION_LEVELS = (0.0, 0.5, 1.0)  # agent.py:268
+
+
+def thermal_arrays(agents) -> Tuple[np.ndarray, np.ndarray]:
+    """What the device needs of each agent's HPHeating / HeatPump (heating.py:92-130), with the
+    reference's casts: levels [N, 3] = f32(level * max_power) (heating.py:124, the product in
+    Python floats) and params [N, 4] = {f32(setpoint), f32(setpoint - 1.0), f32(setpoint + 1.0),
+    f32(cop)} (the bounds formed in f64 and cast afterwards, heating.py:92-94).  Pure NumPy."""
+    levels = np.empty((len(agents), 3), F32)
+    params = np.empty((len(agents), 4), F32)
+    for i, a in enumerate(agents):
+        h = a.heating
+        levels[i] = [F32(l * float(h.hp.max_power)) for l in ACTION_LEVELS]
+        params[i] = [F32(h._temperature_setpoint), F32(h.lower_bound), F32(h.upper_bound), F32(h.hp.cop)]
+    return levels, params
 
 
 class CommunityMicrogrid:
@@ -118,6 +133,15 @@ class CommunityMicrogrid:
             eng.set_profiles(load, pv)
             eng.set_max_in(np.array([F32(a.max_in) for a in self.agents], F32)[None])
             self._uploaded["prof"] = prof_key
+        # every agent's own heat-pump levels, setpoint, comfort band and COP: keyed on the values, so
+        # a change between calls (e.g. agent.heating.hp.max_power = ...) is uploaded again
+        levels, params = thermal_arrays(self.agents)
+        thermal_key = (levels.tobytes(), params.tobytes())
+        if self._uploaded.get("thermal") != thermal_key:
+            eng.set_hp_levels(levels[None])
+            eng.set_thermal(params[None, :, 0], cop=params[None, :, 3], lower=params[None, :, 1],
+                            upper=params[None, :, 2])
+            self._uploaded["thermal"] = thermal_key
         return eng
 
     def _push_temperatures(self, eng):
@@ -168,8 +192,9 @@ class CommunityMicrogrid:
 
     def _pull_records(self, eng, T):
         act = eng.get_record("action")[:, :, 0, :]  # [T, R+1, N]
+        # the power the episode simulated: the uploaded levels are these agents' (_ensure_engine)
         levels = np.array([a.heating.hp.max_power for a in self.agents])
-        self.decisions = np.array([0.0, 0.5, 1.0])[act] * levels[None, None, :]
+        self.decisions = np.array(ACTION_LEVELS)[act] * levels[None, None, :]
         return act
 
     # ------------------------------------------------------------ the reference API
@@ -224,8 +249,6 @@ class CommunityMicrogrid:
                              "tensor_diag_part on the (N, 1) proposal stack fails (community.py:76)")
         eng = self._ensure_engine()
         self._push_temperatures(eng)
-        levels = np.array([[0.0, 0.5, 1.0]], F32) * np.array([[a.heating.hp.max_power] for a in self.agents], F32)
-        eng.set_hp_levels(levels[None])
         eng.set_hp_state(np.array([float(np.asarray(a.heating.hp.power).reshape(-1)[0]) for a in self.agents], F32)[None])
         rec = ("grid", "p2p", "cost", "t_in", "action")
         eng.run_rule_episode(record=rec)

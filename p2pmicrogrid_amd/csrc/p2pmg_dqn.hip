@@ -201,6 +201,7 @@ __global__ __launch_bounds__((dqn_act_waves<NC, WIDE>() * kWave)) void dqn_act_k
     int a;
     float mi, tin, tm, bal, baln, tnorm;
     float4 lv;
+    float4 th;  // the agent's {setpoint, lower, upper, cop} (EpisodeParams::thermal)
     int act;
     float hp, p2pf;
   };
@@ -233,7 +234,8 @@ __global__ __launch_bounds__((dqn_act_waves<NC, WIDE>() * kWave)) void dqn_act_k
     g.tm = p.t_m[g.a];
     g.bal = (f0.x - f0.y) / g.mi;  // RLAgent._get_balance agent.py:172-176
     g.baln = (f1.x - f1.y) / g.mi;
-    g.tnorm = (g.tin - p.setpoint) / p.margin;  // HPHeating.normalized_temperature heating.py:118-120
+    g.th = p.thermal[g.a];
+    g.tnorm = (g.tin - g.th.x) / p.margin;  // HPHeating.normalized_temperature heating.py:118-120
     g.lv = p.hp_lv[g.a];
     g.act = 0;
     g.hp = 0.0f;
@@ -340,7 +342,7 @@ __global__ __launch_bounds__((dqn_act_waves<NC, WIDE>() * kWave)) void dqn_act_k
     cost = cost + pp * p2pp;
     cost = (cost * p.slot) / p.mph;
     cost = cost * p.kilo;
-    float pen = fmaxf(fmaxf(0.0f, p.lower - g.tin), fmaxf(0.0f, g.tin - p.upper));
+    float pen = fmaxf(fmaxf(0.0f, g.th.y - g.tin), fmaxf(0.0f, g.tin - g.th.z));
     pen = pen > 0.0f ? pen + 1.0f : 0.0f;
     const float rw = -(cost + p.penw * pen);
 
@@ -378,7 +380,9 @@ __global__ __launch_bounds__((dqn_act_waves<NC, WIDE>() * kWave)) void dqn_act_k
       if (p.record & 8) p.rec_p2p[kr] = pp;
       if (p.record & 16) p.rec_tin[kr] = g.tin;
       float tin = g.tin, tm = g.tm;
-      rc_update(p, t_out, g.hp, tin, tm);  // HPHeating.step heating.py:138-143
+      // HPHeating.step heating.py:138-143 at the agent's COP
+      const RcParams rc{p.inv_ci, p.inv_cm, p.inv_ri, p.inv_re, p.inv_rvent, p.c_in, p.c_m, p.solar, g.th.w, p.spm, p.slot};
+      rc_update(rc, t_out, g.hp, tin, tm);
       p.t_in[a] = tin;
       p.t_m[a] = tm;
       shR[i] = rw;
@@ -507,6 +511,7 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
   float time_t = 0.0f, t_out = 0.0f, time_n = 0.0f, mi = 1.0f, tin = 0.0f, tm = 0.0f, bal = 0.0f, baln = 0.0f,
         tnorm = 0.0f;
   float4 lv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 tp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the agent's {setpoint, lower, upper, cop}
   if (agent_thr) {
     time_t = e0[0];
     t_out = e0[1];
@@ -520,7 +525,8 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
     tm = p.t_m[a];
     bal = (f0.x - f0.y) / mi;  // RLAgent._get_balance agent.py:172-176
     baln = (f1.x - f1.y) / mi;
-    tnorm = (tin - p.setpoint) / p.margin;  // HPHeating.normalized_temperature heating.py:118-120
+    tp = p.thermal[a];
+    tnorm = (tin - tp.x) / p.margin;  // HPHeating.normalized_temperature heating.py:118-120
     lv = p.hp_lv[a];
   }
   // loaded with the inputs: a load issued after the step's stores would wait for their completion
@@ -691,10 +697,12 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
     cost = cost + pp * p2pp;
     cost = (cost * p.slot) / p.mph;
     cost = cost * p.kilo;
-    float pen = fmaxf(fmaxf(0.0f, p.lower - tin), fmaxf(0.0f, tin - p.upper));
+    float pen = fmaxf(fmaxf(0.0f, tp.y - tin), fmaxf(0.0f, tin - tp.z));
     pen = pen > 0.0f ? pen + 1.0f : 0.0f;
     rw = -(cost + p.penw * pen);
-    rc_update(p, t_out, hp, tin, tm);  // HPHeating.step heating.py:138-143
+    // HPHeating.step heating.py:138-143 at the agent's COP
+    const RcParams rc{p.inv_ci, p.inv_cm, p.inv_ri, p.inv_re, p.inv_rvent, p.c_in, p.c_m, p.solar, tp.w, p.spm, p.slot};
+    rc_update(rc, t_out, hp, tin, tm);
     shR[j] = rw;
   }
   __syncthreads();

@@ -59,6 +59,10 @@ struct EpisodeParams {
   double bat_min, bat_max, bat_sqrt_eff;
   int bat_safe;              // the battery operands lie in battery_rule_r<false>'s verified domain
   const float4* hp_lv;       // [A] per-agent heat-pump power of actions 0..2 (agent.py:268, heating.py:124)
+  // [A] per-agent {setpoint, lower bound, upper bound, COP} (HPHeating / HeatPump, heating.py:92-130).
+  // Every kernel but episode_sq16_kernel reads these, not the scalars below (which fill the array
+  // at p2pmg_create and stay the sq16 kernel's SGPR constants).
+  const float4* thermal;
   void* dummy;               // >= 2 * kWave * 32 B scratch: target of the fast kernel's masked-off stores
   uint32_t* pre_ipc;         // fast path, N = 2: [T][A] round-1 p2p bins for the partner's 3 round-0 actions
   void* rec_pack;            // fast paths: packed records [T][A] x 32 B
@@ -217,10 +221,14 @@ hipError_t launch_philox_codes(const EpisodeParams& p, uint32_t* words, hipStrea
 hipError_t launch_pack_codes(int T, int R1, int A, const uint8_t* in, uint32_t* words, hipStream_t stream);
 hipError_t launch_rc_step(int n, const float* t_out, const float* t_in, const float* t_m, const float* hp,
                           float* t_in_new, float* t_m_new, RcParams rc, hipStream_t stream);
+// ... with per-element COP (cop null: rc.cop) and the caller's solar term in rc.solar
+hipError_t launch_rc_step_ex(int n, const float* t_out, const float* t_in, const float* t_m, const float* hp,
+                             const float* cop, float* t_in_new, float* t_m_new, RcParams rc, hipStream_t stream);
 hipError_t launch_state_indices(int n, const float* obs, int32_t* idx, int nt, int nT, int nb, int np,
                                 hipStream_t stream);
 hipError_t launch_t0_philox(int A, float* t_in, float* t_m, uint32_t seed_lo, uint32_t seed_hi, int episode,
-                            uint32_t agent_offset, float setpoint, double sigma, hipStream_t stream);
+                            uint32_t agent_offset, const float4* thermal /* [A], .x = mean */, double sigma,
+                            hipStream_t stream);
 hipError_t launch_q_pack(int count, size_t n_states, int n_actions, const void* src_ref, void* dst_pad,
                          int q_dtype, int src_dtype, hipStream_t stream);
 hipError_t launch_q_unpack(int count, size_t n_states, int n_actions, const void* src_pad, void* dst_ref,

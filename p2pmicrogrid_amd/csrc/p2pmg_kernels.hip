@@ -256,12 +256,16 @@ struct KC {
   double alpha, gamma;
   int nt, nT, nb, np;
 };
-__device__ __forceinline__ KC pin_constants(const EpisodeParams& p) {
+// Per-agent comfort and heat pump (HPHeating / HeatPump, heating.py:92-130): thermal[a] =
+// {setpoint, lower, upper, cop}, one 16-B load per lane in the kernel's prologue.  The load is
+// unconditional (masked-off lanes read agent 0's entry, as for hp_lv), so its wait is not tied to a
+// branch; the four values are per-lane VGPRs from then on, where the broadcast arguments were pinned.
+__device__ __forceinline__ KC pin_constants(const EpisodeParams& p, const float4 th) {
   KC k;
-  k.setpoint = vpin(p.setpoint); k.margin = vpin(p.margin); k.lower = vpin(p.lower); k.upper = vpin(p.upper);
+  k.setpoint = th.x; k.margin = vpin(p.margin); k.lower = th.y; k.upper = th.z;
   k.inv_ci = vpin(p.inv_ci); k.inv_cm = vpin(p.inv_cm); k.inv_ri = vpin(p.inv_ri); k.inv_re = vpin(p.inv_re);
   k.inv_rvent = vpin(p.inv_rvent); k.c_in = vpin(p.c_in); k.c_m = vpin(p.c_m); k.solar = vpin(p.solar);
-  k.cop = vpin(p.cop); k.spm = vpin(p.spm); k.slot = vpin(p.slot); k.mph = vpin(p.mph); k.kilo = vpin(p.kilo);
+  k.cop = th.w; k.spm = vpin(p.spm); k.slot = vpin(p.slot); k.mph = vpin(p.mph); k.kilo = vpin(p.kilo);
   k.penw = vpin(p.penw);
   k.alpha = vpin(p.alpha); k.gamma = vpin(p.gamma);
   k.nt = vpin(p.nt); k.nT = vpin(p.nT); k.nb = vpin(p.nb); k.np = vpin(p.np);
@@ -274,6 +278,12 @@ __device__ __forceinline__ KC scalar_constants(const EpisodeParams& p) {
   return KC{p.setpoint, p.margin, p.lower, p.upper, p.inv_ci, p.inv_cm, p.inv_ri, p.inv_re, p.inv_rvent,
             p.c_in,     p.c_m,    p.solar, p.cop,   p.spm,    p.slot,   p.mph,    p.kilo,   p.penw,
             p.alpha,    p.gamma,  p.nt,    p.nT,    p.nb,     p.np};
+}
+// ... with the agent's own thermal parameters (rule_episode_kernel)
+__device__ __forceinline__ KC scalar_constants(const EpisodeParams& p, const float4 th) {
+  KC k = scalar_constants(p);
+  k.setpoint = th.x; k.lower = th.y; k.upper = th.z; k.cop = th.w;
+  return k;
 }
 
 // Everything about step t that is known before its negotiation starts.
@@ -581,7 +591,9 @@ __global__ __launch_bounds__((kWave * general_wpb<NC, WIDE, SQ>())) void episode
   const bool margin_one = p.margin == 1.0f;
   const uint32_t rec = (uint32_t)p.record;
   const size_t A = (size_t)p.A;
-  const KC k = pin_constants(p);  // loop constants in VGPRs (no SGPR spill reloads on the chain)
+  // loop constants in VGPRs (no SGPR spill reloads on the chain); setpoint, comfort band and COP are
+  // the agent's own (inactive and out-of-group lanes: agent 0's)
+  const KC k = pin_constants(p, p.thermal[a]);
   const Dims<B20> D{k.nt, k.nT, k.nb, k.np};
   std::conditional_t<WIDE, PTile<NC>, PRegs<NC>> P;
   if constexpr (WIDE) {
@@ -1261,7 +1273,9 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
   const int s_env = p.n_env == 1 ? 0 : (active ? s : 0);
   const int T = p.T;
   const size_t A = (size_t)p.A;
-  const KC k = pin_constants(p);
+  // the agent's setpoint, comfort band and COP: loaded here, before the chain loop, with hp_lv[a],
+  // max_in[a] and t_in[a]; the step loop reads them as the VGPRs the pinned arguments were
+  const KC k = pin_constants(p, p.thermal[a]);
   const uint32_t n_states = (uint32_t)(p.nt * p.nT * p.nb * p.np);
   QT* __restrict__ q = reinterpret_cast<QT*>(p.q) + (size_t)a * n_states * kQPad;  // TD stores
   // Row gathers as ONE 32-bit offset from the wave's first table (global_load's SGPR-base + VGPR-offset
@@ -1374,7 +1388,7 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
     // first rows are in flight, and applied at the end (the f64 transcendentals off the episode tail)
     float t0_in = tin, t0_m = tm;
     if (p.reset_t0 && active)
-      t0_draw(p.seed_lo, p.seed_hi, p.episode + ep + 1, p.agent_offset + (uint32_t)a, p.setpoint, p.reset_sigma, t0_in,
+      t0_draw(p.seed_lo, p.seed_hi, p.episode + ep + 1, p.agent_offset + (uint32_t)a, k.setpoint, p.reset_sigma, t0_in,
               t0_m);
 #if P2PMG_TRACE  // timing-only probe: per-step s_memtime splits of one wave, printed at the end
     uint64_t trW = 0, trC = 0, trR = 0, trLast = 0, trA0 = 0, trWC = 0, trA1 = 0, trMid = 0, trCal = 0;
@@ -2288,8 +2302,8 @@ hipError_t launch_sq16_q(const EpisodeParams& p, hipEvent_t ev0, hipEvent_t ev1,
 // ----------------------------------------------------------------- RuleAgent communities
 // CommunityMicrogrid.run (community.py:95-123) of get_rule_based_community (community.py:237-238):
 // every agent is a RuleAgent (agent.py:106-136), so there is no policy and no exchange round.
-// Per step: the hysteresis rule on the pre-update T_in (on at T_in <= setpoint - 1, off at
-// T_in >= setpoint + 1, else unchanged; agent.py:130-136), net power (load - pv) + hp
+// Per step: the hysteresis rule on the pre-update T_in (on at T_in <= the agent's lower bound, off at
+// T_in >= its upper bound, else unchanged; agent.py:130-136), net power (load - pv) + hp
 // (agent.py:119-128), the market on the (N, 1) stack (TF broadcasts it against its transpose:
 // ex_ij = sign(P_i) min(|P_i|, |P_j|) on differing signs, p_grid_i = sum_j (P_i - ex_ij),
 // community.py:45-54), costs (community.py:56-65), then HPHeating.step (heating.py:138-143).
@@ -2306,7 +2320,7 @@ __global__ __launch_bounds__(kWave) void rule_episode_kernel(const EpisodeParams
   const int a = active ? s * N + i : 0;
   const int s_env = p.n_env == 1 ? 0 : (s < p.S ? s : 0);
   const size_t A = (size_t)p.A;
-  const KC k = scalar_constants(p);
+  const KC k = scalar_constants(p, p.thermal[a]);  // the agent's own thresholds and COP
   const Recip rmph = recip(k.mph);
   const float hpmax = p.hp_lv[a].z;  // HeatPump.max_power (hp.power in {0, 1})
   float on = active ? hp_on[a] : 0.0f;
@@ -2402,6 +2416,18 @@ __global__ void rc_step_kernel(int n, const float* t_out, const float* t_in, con
   t_in_new[k] = a;
   t_m_new[k] = b;
 }
+// ... with one COP per element (cop == null: rc.cop) and the caller's solar term in rc.solar
+// (heating.temperature_simulation with hp_cop / solar_rad, heating.py:37-56)
+__global__ void rc_step_ex_kernel(int n, const float* t_out, const float* t_in, const float* t_m, const float* hp,
+                                  const float* cop, float* t_in_new, float* t_m_new, RcParams rc) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  if (cop) rc.cop = cop[k];
+  float a = t_in[k], b = t_m[k];
+  rc_update(rc, t_out[k], hp[k], a, b);
+  t_in_new[k] = a;
+  t_m_new[k] = b;
+}
 #endif
 
 #if P2PMG_IN_PART(0)
@@ -2418,10 +2444,11 @@ __global__ void state_indices_kernel(int n, const float* obs, int32_t* idx, int 
 
 #if P2PMG_IN_PART(0)
 __global__ void t0_philox_kernel(int A, float* t_in, float* t_m, uint32_t k0, uint32_t k1, int episode,
-                                 uint32_t agent_offset, float setpoint, double sigma) {
+                                 uint32_t agent_offset, const float4* __restrict__ thermal, double sigma) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= A) return;
-  t0_draw(k0, k1, episode, agent_offset + (uint32_t)k, setpoint, sigma, t_in[k], t_m[k]);
+  // T0 ~ N(setpoint_a, sigma): the agent's own mean (t0_draw widens it to f64 before the add)
+  t0_draw(k0, k1, episode, agent_offset + (uint32_t)k, thermal[k].x, sigma, t_in[k], t_m[k]);
 }
 #endif
 
@@ -2769,6 +2796,13 @@ hipError_t launch_rc_step(int n, const float* t_out, const float* t_in, const fl
                      t_m_new, rc);
   return hipGetLastError();
 }
+hipError_t launch_rc_step_ex(int n, const float* t_out, const float* t_in, const float* t_m, const float* hp,
+                             const float* cop, float* t_in_new, float* t_m_new, RcParams rc, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(rc_step_ex_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, n, t_out, t_in, t_m, hp, cop,
+                     t_in_new, t_m_new, rc);
+  return hipGetLastError();
+}
 #endif
 
 #if P2PMG_IN_PART(0)
@@ -2782,10 +2816,10 @@ hipError_t launch_state_indices(int n, const float* obs, int32_t* idx, int nt, i
 
 #if P2PMG_IN_PART(0)
 hipError_t launch_t0_philox(int A, float* t_in, float* t_m, uint32_t seed_lo, uint32_t seed_hi, int episode,
-                            uint32_t agent_offset, float setpoint, double sigma, hipStream_t stream) {
+                            uint32_t agent_offset, const float4* thermal, double sigma, hipStream_t stream) {
   if (A <= 0) return hipSuccess;
   hipLaunchKernelGGL(t0_philox_kernel, dim3(grid_for(A, 256)), dim3(256), 0, stream, A, t_in, t_m, seed_lo, seed_hi,
-                     episode, agent_offset, setpoint, sigma);
+                     episode, agent_offset, thermal, sigma);
   return hipGetLastError();
 }
 #endif

@@ -87,6 +87,8 @@ struct p2pmg_ctx {
   void* rec_stage = nullptr;  // fast / sq16 launches: one staging buffer the packed rows unpack into
   size_t rec_stage_bytes = 0;
   float4* hp_lv = nullptr;     // [A] per-agent heat-pump levels
+  float4* thermal = nullptr;   // [A] per-agent {setpoint, lower bound, upper bound, COP} (p2pmg_set_thermal)
+  bool thermal_set = false;    // p2pmg_set_thermal uploaded values (false: the config's, where sq16 applies)
   float* hp_on = nullptr;      // [A] RuleAgent heat-pump state (lazily allocated, starts off)
   double* soc = nullptr;       // [A]
   double* bat_cap = nullptr;   // [A]
@@ -330,11 +332,16 @@ int p2pmg_create(const p2pmg_config* cfg, int device, p2pmg_ctx** out) {
     if (hipMemsetAsync(c->qdelta, 0, p2pmg::kDeltaCopies * c->n_states * kQPad * 8, c->stream) != hipSuccess)
       return bail(P2PMG_E_HIP);
   }
-  if (dmalloc(&c->hp_lv, A) != hipSuccess || dmalloc(&c->soc, A) != hipSuccess) return bail(P2PMG_E_NOMEM);
+  if (dmalloc(&c->hp_lv, A) != hipSuccess || dmalloc(&c->soc, A) != hipSuccess || dmalloc(&c->thermal, A) != hipSuccess)
+    return bail(P2PMG_E_NOMEM);
   {
     std::vector<float4> lv(A, make_float4(cfg->hp_levels[0], cfg->hp_levels[1], cfg->hp_levels[2], 0.0f));
+    // the config's scalars for every agent: a context that never calls p2pmg_set_thermal computes
+    // what the broadcast kernel arguments did
+    std::vector<float4> th(A, make_float4(cfg->setpoint, cfg->lower_bound, cfg->upper_bound, cfg->hp_cop));
     std::vector<double> s0(A, 0.5);
     if (hipMemcpyAsync(c->hp_lv, lv.data(), A * sizeof(float4), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(c->thermal, th.data(), A * sizeof(float4), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(c->soc, s0.data(), A * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess)
       return bail(P2PMG_E_HIP);
@@ -377,6 +384,7 @@ int p2pmg_destroy(p2pmg_ctx* c) {
   dfree(c->rec_index);
   if (c->rec_stage) (void)hipFree(c->rec_stage);
   dfree(c->hp_lv);
+  dfree(c->thermal);
   dfree(c->hp_on);
   dfree(c->soc);
   dfree(c->bat_cap);
@@ -519,7 +527,7 @@ int p2pmg_reset_temperatures_philox(p2pmg_ctx* c, int episode, double sigma) {
   if (!c) return P2PMG_E_INVALID;
   const uint32_t off = (uint32_t)(c->cfg.scenario_offset * c->N);
   HIP_TRY(c, p2pmg::launch_t0_philox(c->A, c->t_in, c->t_m, (uint32_t)(c->cfg.seed & 0xFFFFFFFFu),
-                                     (uint32_t)(c->cfg.seed >> 32), episode, off, c->cfg.setpoint, sigma, c->stream));
+                                     (uint32_t)(c->cfg.seed >> 32), episode, off, c->thermal, sigma, c->stream));
   return P2PMG_OK;
 }
 
@@ -637,6 +645,7 @@ static EpisodeParams episode_params(p2pmg_ctx* c, const p2pmg_episode_args* args
   p.bat_max = c->bat_max;
   p.bat_sqrt_eff = c->bat_sqrt_eff;
   p.hp_lv = c->hp_lv;
+  p.thermal = c->thermal;
   p.dummy = c->dummy;
   p.nt = g.n_time_states;
   p.nT = g.n_temp_states;
@@ -729,6 +738,7 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
                     (long long)c->T * c->A < (1LL << 32) && (long long)c->T * c->n_env * p2pmg::kEnvStride < (1LL << 32) &&
                     host_div_range(g.temp_margin) && g.n_time_states == 20 && g.n_temp_states == 20 &&
                     g.n_balance_states == 20 && g.n_p2p_states == 20 &&
+                    !c->thermal_set &&  // per-agent thermal parameters: the general kernel's shared-table form
                     !(args->flags & (P2PMG_FLAG_GENERAL_KERNEL | P2PMG_FLAG_TILE_KERNEL)) && !env_general;
   // the general kernel writes unpacked records; fast / sq16 write packed rows (rec_pack) that
   // p2pmg_get_record unpacks into one staging buffer, so those launches allocate no [T][A] arrays
@@ -885,7 +895,7 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
   if (reset && !ext) {  // general kernel: the reset as its own launch
     const uint32_t off = (uint32_t)(g.scenario_offset * c->N);
     HIP_TRY(c, p2pmg::launch_t0_philox(c->A, c->t_in, c->t_m, p.seed_lo, p.seed_hi, args->episode + 1, off,
-                                       g.setpoint, args->reset_sigma, c->stream));
+                                       c->thermal, args->reset_sigma, c->stream));
   }
   c->timed = true;
   if (stamp) c->n_timed++;
@@ -1148,6 +1158,32 @@ int p2pmg_rc_step(p2pmg_ctx* c, int n, const float* t_out, const float* t_in, co
   return P2PMG_OK;
 }
 
+int p2pmg_rc_step_ex(p2pmg_ctx* c, int n, const float* t_out, const float* t_in, const float* t_m, const float* hp,
+                     const float* cop, float solar_gain, float* t_in_new, float* t_m_new) {
+  if (!c || n < 0 || !t_out || !t_in || !t_m || !hp || !t_in_new || !t_m_new) return P2PMG_E_INVALID;
+  if (n == 0) return P2PMG_OK;
+  float* d = nullptr;
+  HIP_TRY(c, dmalloc(&d, (size_t)7 * n));
+  const size_t b = (size_t)n * 4, sn = (size_t)n;
+  hipError_t e = hipMemcpyAsync(d, t_out, b, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d + sn, t_in, b, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * sn, t_m, b, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d + 3 * sn, hp, b, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && cop) e = hipMemcpyAsync(d + 6 * sn, cop, b, hipMemcpyHostToDevice, c->stream);
+  const p2pmg_config& g = c->cfg;
+  p2pmg::RcParams rc{g.inv_ci, g.inv_cm, g.inv_ri, g.inv_re, g.inv_rvent, g.one_minus_frad,
+                     g.frad, solar_gain, g.hp_cop, g.seconds_per_minute, g.time_slot};
+  if (e == hipSuccess)
+    e = p2pmg::launch_rc_step_ex(n, d, d + sn, d + 2 * sn, d + 3 * sn, cop ? d + 6 * sn : nullptr, d + 4 * sn,
+                                 d + 5 * sn, rc, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(t_in_new, d + 4 * sn, b, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(t_m_new, d + 5 * sn, b, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dfree(d);
+  if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("rc_step_ex: ") + hipGetErrorString(e));
+  return P2PMG_OK;
+}
+
 extern "C++" template <typename T, typename L>
 static int div_check(p2pmg_ctx* c, int n, const T* a, const T* b, T* out, int per, L launch, const char* what) {
   if (!c || n < 0 || (n > 0 && (!a || !b || !out))) return P2PMG_E_INVALID;
@@ -1207,6 +1243,49 @@ int p2pmg_set_hp_levels(p2pmg_ctx* c, const float* levels) {
   }
   c->hp_bounded = ok;
   HIP_TRY(c, hipMemcpyAsync(c->hp_lv, lv.data(), lv.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return P2PMG_OK;
+}
+
+int p2pmg_get_hp_levels(p2pmg_ctx* c, float* levels) {
+  if (!c || !levels) return P2PMG_E_INVALID;
+  std::vector<float4> lv((size_t)c->A);
+  HIP_TRY(c, hipMemcpyAsync(lv.data(), c->hp_lv, lv.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t a = 0; a < lv.size(); ++a) {
+    levels[3 * a] = lv[a].x;
+    levels[3 * a + 1] = lv[a].y;
+    levels[3 * a + 2] = lv[a].z;
+  }
+  return P2PMG_OK;
+}
+
+int p2pmg_set_thermal(p2pmg_ctx* c, const float* params) {
+  if (!c) return P2PMG_E_INVALID;
+  const p2pmg_config& g = c->cfg;
+  std::vector<float4> th((size_t)c->A, make_float4(g.setpoint, g.lower_bound, g.upper_bound, g.hp_cop));
+  if (params) {
+    for (size_t a = 0; a < th.size(); ++a) {
+      const float* v = params + 4 * a;
+      if (!(std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]) && std::isfinite(v[3])))
+        return fail(c, P2PMG_E_INVALID, "set_thermal: non-finite value for agent " + std::to_string(a));
+      if (v[1] > v[2])
+        return fail(c, P2PMG_E_INVALID, "set_thermal: lower bound above upper bound for agent " + std::to_string(a));
+      th[a] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+  }
+  // the step pre-pass reads none of these (it depends on the inputs and heat-pump levels only), so the
+  // speculative slots stay valid
+  HIP_TRY(c, hipMemcpyAsync(c->thermal, th.data(), th.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->thermal_set = params != nullptr;
+  return P2PMG_OK;
+}
+
+int p2pmg_get_thermal(p2pmg_ctx* c, float* params) {
+  if (!c || !params) return P2PMG_E_INVALID;
+  static_assert(sizeof(float4) == 4 * sizeof(float), "thermal rows are 4 packed floats");
+  HIP_TRY(c, hipMemcpyAsync(params, c->thermal, (size_t)c->A * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return P2PMG_OK;
 }

@@ -160,6 +160,37 @@ class DeviceCommunityBatch:
         lv = np.ascontiguousarray(np.asarray(levels, dtype=F32).reshape(self.A, 3))
         self._chk(self.L.p2pmg_set_hp_levels(self._ctx, lv), "set_hp_levels")
 
+    def get_hp_levels(self) -> np.ndarray:
+        """[S, N, 3] f32: the heat-pump power per action the kernels read."""
+        out = np.empty((self.A, 3), F32)
+        self._chk(self.L.p2pmg_get_hp_levels(self._ctx, out), "get_hp_levels")
+        return out.reshape(self.S, self.N, 3)
+
+    def set_thermal(self, setpoint, cop=None, lower=None, upper=None):
+        """Per-agent comfort setpoint and heat-pump COP (HPHeating / HeatPump, heating.py:92-130):
+        [S, N] arrays or scalars.  lower / upper default to the reference's bounds, formed in f64
+        and cast afterwards: f32(float64(setpoint) -/+ 1.0) (heating.py:92-94).  cop None: the
+        config's.  set_thermal(None) restores the config's values for every agent."""
+        if setpoint is None:
+            self._chk(self.L.p2pmg_set_thermal(self._ctx, None), "set_thermal")
+            return
+        def per_agent(x):
+            return np.broadcast_to(np.asarray(x, np.float64), (self.S, self.N)).reshape(self.A)
+        sp = per_agent(setpoint)
+        margin = float(self.cfg.temp_margin)  # HPHeating.TEMPERATURE_MARGIN = 1
+        par = np.empty((self.A, 4), F32)
+        par[:, 0] = sp.astype(F32)
+        par[:, 1] = (sp - margin).astype(F32) if lower is None else per_agent(lower).astype(F32)
+        par[:, 2] = (sp + margin).astype(F32) if upper is None else per_agent(upper).astype(F32)
+        par[:, 3] = F32(self.cfg.hp_cop) if cop is None else per_agent(cop).astype(F32)
+        self._chk(self.L.p2pmg_set_thermal(self._ctx, par.ctypes.data), "set_thermal")
+
+    def get_thermal(self) -> np.ndarray:
+        """[S, N, 4] f32 {setpoint, lower bound, upper bound, COP} the kernels read."""
+        out = np.empty((self.A, 4), F32)
+        self._chk(self.L.p2pmg_get_thermal(self._ctx, out), "get_thermal")
+        return out.reshape(self.S, self.N, 4)
+
     def set_battery(self, capacity=None, min_soc=0.1, max_soc=0.9, efficiency=0.9, soc0=None):
         """Battery per agent (capacity [S, N] in J, 0 = none); None disables storage."""
         if capacity is None:
@@ -370,14 +401,21 @@ class DeviceCommunityBatch:
         return out
 
     # ----------------------------------------------------------------- primitives
-    def rc_step(self, t_out, t_in, t_m, hp):
-        """Batched heating.temperature_simulation (heating.py:37-56) on the device."""
-        arrs = [np.ascontiguousarray(np.asarray(x, dtype=F32).ravel()) for x in np.broadcast_arrays(t_out, t_in, t_m, hp)]
+    def rc_step(self, t_out, t_in, t_m, hp, cop=None, solar_gain=0.0):
+        """Batched heating.temperature_simulation (heating.py:37-56) on the device.
+        cop: per-element COP (None: the config's); solar_gain: f32(gA * solar_rad).  With either
+        given the call is p2pmg_rc_step_ex, else p2pmg_rc_step."""
+        ins = (t_out, t_in, t_m, hp) if cop is None else (t_out, t_in, t_m, hp, cop)
+        arrs = [np.ascontiguousarray(np.asarray(x, dtype=F32).ravel()) for x in np.broadcast_arrays(*ins)]
         n = arrs[0].size
         a = np.empty(n, F32)
         b = np.empty(n, F32)
-        self._chk(self.L.p2pmg_rc_step(self._ctx, n, *arrs, a, b), "rc_step")
-        shape = np.broadcast(t_out, t_in, t_m, hp).shape
+        if cop is None and float(solar_gain) == 0.0:
+            self._chk(self.L.p2pmg_rc_step(self._ctx, n, *arrs, a, b), "rc_step")
+        else:
+            self._chk(self.L.p2pmg_rc_step_ex(self._ctx, n, *arrs[:4], None if cop is None else arrs[4].ctypes.data,
+                                              F32(solar_gain), a, b), "rc_step_ex")
+        shape = np.broadcast(*ins).shape
         return a.reshape(shape), b.reshape(shape)
 
     def fdiv_check(self, a, b):

@@ -1,7 +1,8 @@
 """Heat-pump heating and the 2-node RC thermal model (mirrors microgrid/heating.py:17-163).
 
 ``temperature_simulation`` keeps the reference signature but runs batched on the device
-(p2pmg_rc_step): scalars or arrays of any matching shape.  ``HPHeating`` holds an agent's
+(p2pmg_rc_step, or p2pmg_rc_step_ex for another COP or a solar term): scalars or arrays of any
+matching shape.  ``HPHeating`` holds an agent's
 thermal parameters and its T_in / T_m between episodes; during an episode the state lives in
 the kernel's registers.
 """
@@ -42,12 +43,15 @@ def _primitives():
 
 def temperature_simulation(t_out, t_in, t_bm, hp_power, hp_cop: float = 3.0,
                            solar_rad: float = 0) -> Tuple[np.ndarray, np.ndarray]:
-    """heating.py:37-56 on the device, f32 with the reference's constant casts.  Only the
-    reference's constants are compiled into the primitive: hp_cop must be 3.0 and solar_rad 0
-    (the values every reference caller uses, community.py:226)."""
-    if float(hp_cop) != 3.0 or float(solar_rad) != 0.0:
-        raise NotImplementedError("temperature_simulation: only hp_cop=3.0, solar_rad=0 are supported")
-    a, b = _primitives().rc_step(t_out, t_in, t_bm, hp_power)
+    """heating.py:37-56 on the device, f32 with the reference's constant casts.  hp_cop is a
+    scalar or an array that broadcasts against the temperatures (one COP per element, cast to
+    f32 as TF casts the Python float); solar_rad enters as the f32 constant f32(gA * solar_rad)
+    of heating.py:49.  The reference's own callers pass hp_cop = 3.0 and no solar_rad
+    (community.py:226), which is p2pmg_rc_step; anything else is p2pmg_rc_step_ex."""
+    solar_gain = np.float32(gA * float(solar_rad))
+    default_cop = np.ndim(hp_cop) == 0 and float(hp_cop) == 3.0
+    a, b = _primitives().rc_step(t_out, t_in, t_bm, hp_power, cop=None if default_cop else hp_cop,
+                                 solar_gain=solar_gain)
     if np.ndim(a) == 0:
         return np.float32(a), np.float32(b)
     return a, b
