@@ -113,12 +113,33 @@ typedef struct p2pmg_config {
                               1: one shared policy table for every agent of every scenario
                               (config 3, build-defined): frozen during an episode, TD deltas summed
                               in int64 fixed point (2^-40) and applied by p2pmg_apply_q_delta;
-                              with learner = DQN: one shared Q-network (config 5, data-parallel) */
-  int32_t learner;         /* P2PMG_LEARNER_TABULAR (QAgent) | P2PMG_LEARNER_DQN (DQNAgent) */
+                              with learner = DQN: one shared Q-network (config 5, data-parallel);
+                              P2PMG_SHARED_ROLE (2): one table per role, see below.  Any other non-zero
+                              value means 1, as every non-zero value did before 2 was defined */
+  int32_t learner;        /* P2PMG_LEARNER_TABULAR (QAgent) | P2PMG_LEARNER_DQN (DQNAgent) */
 } p2pmg_config;
 
 #define P2PMG_LEARNER_TABULAR 0
 #define P2PMG_LEARNER_DQN 1
+
+/* p2pmg_config.shared_q = P2PMG_SHARED_ROLE: one policy table per ROLE, a role being an agent's
+ * position i in its community (the reference's one QActor per agent of ONE community, rl.py:73,
+ * agent.py:263, run over S scenarios: days, weather, T0 draws, exploration streams).  The context
+ * holds exactly N tables and agent (s, i) of every scenario s reads table i.  Like shared_q = 1 the
+ * tables are frozen during an episode; in TRAIN mode agent (s, i)'s update
+ * llrint(alpha * ((r + gamma * max Q_i[ns]) - Q_i[s, a]) * 2^40) is summed into role i's int64
+ * delta and p2pmg_apply_q_delta does Q_i += delta_i * 2^-40 for every role; GREEDY only reads.  At
+ * N = 1 this is shared_q = 1 bit for bit.
+ *   - p2pmg_set_q / get_q / zero_q address tables 0..N-1; p2pmg_get_q_delta / set_q_delta move
+ *     [N][n_states][n_actions]; apply_q_delta, allreduce_q_delta and table_hash_allgather cover all N.
+ *   - the general episode kernel's shared-table form runs it (p2pmg_last_kernel: "...,shared,roles>"),
+ *     never episode_fast_kernel or episode_sq16_kernel; p2pmg_set_battery, p2pmg_set_hp_levels and
+ *     p2pmg_set_thermal work as with shared_q = 1.
+ *   - learner = DQN: p2pmg_create returns P2PMG_E_UNSUPPORTED (p2pmg_last_error(NULL) on the calling
+ *     thread says why); a Q-network per role is not built.
+ *   - memory: N tables of n_states x 4 elements (5.1 MB each in f64 at 20^4 states) and a delta
+ *     buffer of 8 copies x N x 5.1 MB of int64 (2.6 GB at N = 64). */
+#define P2PMG_SHARED_ROLE 2
 
 typedef struct p2pmg_episode_args {
   int32_t mode;     /* P2PMG_MODE_TRAIN | P2PMG_MODE_GREEDY */
@@ -264,9 +285,9 @@ int p2pmg_battery_seq(p2pmg_ctx* ctx, int agents, int steps, const double* balan
                       double* out_balance, double* soc_hist, double* soc /* [agents] in/out */,
                       const double* capacity, double min_soc, double max_soc, double efficiency);
 
-/* shared policy table (config.shared_q = 1) */
+/* shared policy table (config.shared_q = 1), or the N per-role tables (P2PMG_SHARED_ROLE) */
 int p2pmg_apply_q_delta(p2pmg_ctx* ctx);            /* Q += delta * 2^-40; delta = 0 */
-int p2pmg_get_q_delta(p2pmg_ctx* ctx, int64_t* host); /* [n_states][n_actions] fixed point */
+int p2pmg_get_q_delta(p2pmg_ctx* ctx, int64_t* host); /* [n_states][n_actions] fixed point ([N][...] per role) */
 int p2pmg_set_q_delta(p2pmg_ctx* ctx, const int64_t* host); /* e.g. after a host-side (gloo) sum */
 
 /* multi-GPU exchange of the shared-table deltas over RCCL (xGMI), loaded at run time */

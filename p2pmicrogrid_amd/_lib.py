@@ -18,6 +18,7 @@ STATUS = {0: "OK", 1: "INVALID", 2: "HIP", 3: "NOMEM", 4: "STATE", 5: "UNSUPPORT
 Q_F64, Q_F32 = 0, 1
 MODE_TRAIN, MODE_GREEDY, MODE_FILL = 0, 1, 2
 LEARNER_TABULAR, LEARNER_DQN = 0, 1
+SHARED_ROLE = 2  # Config.shared_q: one table per agent position (P2PMG_SHARED_ROLE)
 DQN_ONLINE, DQN_TARGET, DQN_ADAM_M, DQN_ADAM_V = 0, 1, 2, 3
 DQN_PARAMS = 4609
 RNG_REPLAY, RNG_PHILOX = 0, 1

@@ -242,6 +242,53 @@ class CommunityMicrogrid:
         power = (r["grid"][:, 0, :] + r["p2p"][:, 0, :]).astype(F32)
         return power, r["cost"][:, 0, :]
 
+    def run_days(self, days) -> List[Dict[str, np.ndarray]]:
+        """run() of this community over several days in ONE greedy launch: a per-role-table engine
+        (``shared_q="role"``) with one scenario per day, holding one copy of every agent's table
+        instead of one per day.  ``days``: a sequence of dicts {"time" [T], "t_out" [T], "load" [N, T],
+        "pv" [N, T] (W), "t_in" [N], "t_m" [N]}, all of one length T.  Returns, per day, "power" and
+        "cost" [T, N] and "decisions" [T, R + 1, N] as run() gives them, plus "t_in" [T, N] (T_in before
+        each step) and "t_in_final" / "t_m_final" [N].  Each day is bit for bit what run() computes
+        from that day's inputs.  The agents' tables are read, nothing else of the community changes.
+        Tabular communities only."""
+        if self._rule or self._dqn:
+            raise NotImplementedError("run_days needs tabular (QAgent) agents: per-role tables hold Q-tables, "
+                                      "and a RuleAgent community has no policy to share")
+        if self._battery_rule and any(self._batteries()):
+            raise NotImplementedError("run_days does not carry battery state across days")
+        D, N = len(days), len(self.agents)
+        if D == 0:
+            return []
+        T = len(np.asarray(days[0]["time"]).reshape(-1))
+
+        def stack(key, shape):
+            return np.stack([np.asarray(d[key], F32).reshape(shape) for d in days])
+        time_f, t_out = stack("time", (T,)), stack("t_out", (T,))
+        eng = DeviceCommunityBatch(D, N, self._rounds, T, q_dtype=self._q_dtype, device=self._device, shared_q="role")
+        try:
+            eng.set_q(np.stack([a.actor.q_table for a in self.agents]))
+            eng.set_env(time_f, t_out, *price_table(time_f))
+            eng.set_profiles(stack("load", (N, T)), stack("pv", (N, T)))
+            eng.set_max_in(np.broadcast_to(np.array([F32(a.max_in) for a in self.agents], F32), (D, N)))
+            levels, params = thermal_arrays(self.agents)
+            eng.set_hp_levels(np.broadcast_to(levels, (D, N, 3)))
+            par = np.broadcast_to(params, (D, N, 4))
+            eng.set_thermal(par[..., 0], cop=par[..., 3], lower=par[..., 1], upper=par[..., 2])
+            eng.set_temperatures(stack("t_in", (N,)), stack("t_m", (N,)))
+            rec = ("grid", "p2p", "cost", "t_in", "action")
+            eng.run_episode("greedy", record=rec)
+            r = eng.get_records(rec)
+            t_in, t_m = eng.get_temperatures()
+        finally:
+            eng.close()
+        max_power = np.array([a.heating.hp.max_power for a in self.agents])
+        out = []
+        for d in range(D):
+            out.append({"power": (r["grid"][:, d, :] + r["p2p"][:, d, :]).astype(F32), "cost": r["cost"][:, d, :],
+                        "decisions": np.array(ACTION_LEVELS)[r["action"][:, :, d, :]] * max_power[None, None, :],
+                        "t_in": r["t_in"][:, d, :], "t_in_final": t_in[d], "t_m_final": t_m[d]})
+        return out
+
     def _run_rule(self) -> Tuple[np.ndarray, np.ndarray]:
         """run() of a RuleAgent community: one rule_episode_kernel launch (R = 0)."""
         if self._rounds != 0:
@@ -536,4 +583,51 @@ def load_and_run(con=None, is_testing: bool = False, analyse: bool = True) -> Di
         if con is not None:
             save_community_results(con, is_testing, setting, int(day), community, np.asarray(cost))
         out[int(day)] = {"power": power, "cost": cost, "decisions": community.decisions.copy()}
+    return out
+
+
+def load_and_run_batched(con=None, is_testing: bool = False) -> Dict[int, Dict[str, np.ndarray]]:
+    """load_and_run with every day in ONE greedy launch (CommunityMicrogrid.run_days): the same per-day
+    results, bit for bit, the same DB rows and the same np.random consumption.  The day-by-day loop
+    draws, per day, community.reset()'s T0 and then _set_day_profiles' scales and resets; the greedy
+    launch draws nothing, so all of that is drawn first, day after day in that order, and each day's
+    inputs are kept for the launch.  Tabular communities only."""
+    setting = setting_name()
+    community = get_rl_based_community(setup.nr_agents, homogeneous=setup.homogeneous)
+    for agent in community.agents:
+        agent.load_from_file(setting, setup.implementation)
+    env_df, agent_dfs = ds.get_test_data() if is_testing else ds.get_validation_data()
+    days = np.unique(env_df['day'])
+    day_indices = {day: env_df['day'] == day for day in days}
+    env_df = env_df.drop(axis=1, labels='day')
+    if setup.homogeneous:
+        agent_dfs = [agent_dfs[0]] * setup.nr_agents
+    inputs, held = [], []
+    for day in days:
+        day_env = ds.dataframe_to_dataset(env_df[day_indices[day]])
+        env.setup(day_env)
+        community.reset()
+        _set_day_profiles(community, agent_dfs, day_indices[day])
+        time_f, t_out = env.arrays()
+        T = len(time_f)
+        inputs.append({"time": time_f, "t_out": t_out,
+                       "load": np.stack([a.load_series(T) for a in community.agents]),
+                       "pv": np.stack([a.pv.series(T) for a in community.agents]),
+                       "t_in": np.array([a.heating.temperature[0] for a in community.agents], F32),
+                       "t_m": np.array([a.heating.building_mass_temperature[0] for a in community.agents], F32)})
+        held.append((day_env, [(a._load, a.pv.pv.production) for a in community.agents]))
+    results = community.run_days(inputs)
+    out = {}
+    for day, (day_env, profiles), res in zip(days, held, results):
+        # the community as run() leaves it after this day: what save_community_results reads
+        env.setup(day_env)
+        community.decisions = res["decisions"]
+        for i, (a, (load, pv)) in enumerate(zip(community.agents, profiles)):
+            a._load, a.pv.pv.production = load, pv
+            a.heating._history = [float(x) for x in res["t_in"][:, i]]
+            a.heating._power_history = list(res["decisions"][:, -1, i])
+            a.heating.set_state(res["t_in_final"][i], res["t_m_final"][i])
+        if con is not None:
+            save_community_results(con, is_testing, setting, int(day), community, np.asarray(res["cost"]))
+        out[int(day)] = {"power": res["power"], "cost": res["cost"], "decisions": res["decisions"].copy()}
     return out

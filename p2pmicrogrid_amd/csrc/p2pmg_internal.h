@@ -50,8 +50,8 @@ struct EpisodeParams {
   float* ep_reward;          // [S]
   // shared policy (config 3): every agent reads one frozen table; TD deltas accumulate in
   // int64 fixed point (2^-40) with device atomics, applied at episode end (p2pmg_apply_q_delta)
-  int shared_q;
-  long long* qdelta;         // [kDeltaCopies][n_states][kQPad] int64 (one replica per XCD)
+  int shared_q;              // 0 per-agent tables, 1 one table, 2 one table per role (agent position): [N] tables
+  long long* qdelta;         // [kDeltaCopies][tables][n_states][kQPad] int64 (one replica per XCD)
   // battery (agent.py:138-153 rule, storage.py:36-76 bookkeeping), f64 like the reference
   int battery;
   double* soc;               // [A] in/out
@@ -201,6 +201,11 @@ hipError_t launch_general_part7(const EpisodeParams& p, int q_dtype, hipStream_t
 hipError_t launch_general_part8(const EpisodeParams& p, int q_dtype, hipStream_t stream);
 hipError_t launch_tile_part9(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
 hipError_t launch_tile_part10(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
+// per-role tables (p.shared_q == 2); nc = 0: the register form
+hipError_t launch_role_part11(const EpisodeParams& p, int q_dtype, hipStream_t stream);
+hipError_t launch_role_part12(const EpisodeParams& p, int q_dtype, hipStream_t stream);
+hipError_t launch_role_part13(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
+hipError_t launch_role_part14(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
 // RuleAgent community run (R = 0): rule_episode_kernel; hp_on [A] hysteresis state in/out
 hipError_t launch_rule_episode(const EpisodeParams& p, float* hp_on, hipStream_t stream);
 // shared table, N = 16, R <= 1 (configs[2]): episode_sq16_kernel; records packed like the fast path

@@ -26,6 +26,8 @@
 //   0: small kernels + dispatchers   1-4: episode_fast_kernel, N = 1-2 / 3-4 / 5-6 / 7-8
 //   5: episode_sq16_kernel           6-8: episode_kernel, N = 1-4 / 5-8 / 16
 //   9-10: episode_kernel's LDS-tile form, up to 16 / 32 and 64 agents
+//   11-14: episode_kernel's per-role-table form (shared_q = 2), N = 1-4 / 5-8 / 16 and tiles of 16 /
+//          tiles of 32 and 64
 // Without -DP2PMG_PART everything is in one translation unit.
 #ifndef P2PMG_PART
 #define P2PMG_PART -1
@@ -554,10 +556,13 @@ constexpr int general_wpb() {
 // (PRegs); WIDE = true: n = p.N <= NC agents (PTile), the community sizes 9..15 and 17..64.  Both
 // sum over j = 0..n-1 in order from +0.0 and divide by n as IEEE quotients, so a scenario gives the
 // same bits either way (tests/test_gpu_parity.py runs the tile form at the register form's sizes).
-template <int NC, bool WIDE, typename QT, bool B20, bool SQ>
+// ROLE (with SQ): one frozen table per agent position ("role") i instead of one for all: lane i
+// reads table i and its delta keys are offset by i tables, inside a delta replica of n tables.
+template <int NC, bool WIDE, typename QT, bool B20, bool SQ, bool ROLE = false>
 __global__ __launch_bounds__((kWave * general_wpb<NC, WIDE, SQ>())) void episode_kernel(const EpisodeParams p) {
   constexpr int G = pow2ceil(NC);
   constexpr int SPW = kWave / G;
+  static_assert(SQ || !ROLE, "per-role tables are a shared-table form");
   constexpr int WPB = general_wpb<NC, WIDE, SQ>();  // waves per workgroup
   constexpr int PW = WIDE ? SPW * 2 * PTile<NC>::kTile : (G > 8 ? SPW * NC * NC : 1);
   constexpr int RW = (WIDE || G > 8) ? SPW * NC : 1;
@@ -601,6 +606,10 @@ __global__ __launch_bounds__((kWave * general_wpb<NC, WIDE, SQ>())) void episode
     P.i = i;
     P.rd = 0;
     P.wr = 0;
+    // lanes i >= n read columns and rows no put() writes (their results are dropped, but the values
+    // reach idx_plain and a gather address): give them zeros, once
+    for (int k2 = lane; k2 < PW; k2 += kWave) shP[k2] = 0.0f;
+    wave_lds_fence();
   } else {
     P.sh = shP;
     P.i = i;
@@ -609,9 +618,12 @@ __global__ __launch_bounds__((kWave * general_wpb<NC, WIDE, SQ>())) void episode
 
   const uint32_t n_states = (uint32_t)(p.nt * p.nT * p.nb * p.np);
   constexpr bool shared = SQ;
-  QT* __restrict__ q = reinterpret_cast<QT*>(p.q) + (shared ? (size_t)0 : (size_t)a * n_states * kQPad);
+  // per-role tables: at most 64 x 640,000 entries, so a role's key offset fits 32 bits well below
+  // kSqEmpty; inactive and out-of-group lanes read role 0
+  const uint32_t role_off = ROLE ? (uint32_t)(active ? i : 0) * n_states * kQPad : 0u;
+  QT* __restrict__ q = reinterpret_cast<QT*>(p.q) + (shared ? (size_t)role_off : (size_t)a * n_states * kQPad);
   unsigned long long* const dbase = reinterpret_cast<unsigned long long*>(p.qdelta) +
-      (shared ? (size_t)(blockIdx.x % kDeltaCopies) * n_states * kQPad : (size_t)0);
+      (shared ? (size_t)(blockIdx.x % kDeltaCopies) * (ROLE ? (size_t)n : (size_t)1) * n_states * kQPad : (size_t)0);
   if constexpr (SQ) {
     for (int k2 = threadIdx.x; k2 < kSqSlots; k2 += WPB * kWave) {
       hkey[k2] = kSqEmpty;
@@ -791,7 +803,7 @@ __global__ __launch_bounds__((kWave * general_wpb<NC, WIDE, SQ>())) void episode
 #if P2PMG_ABLATE == 5
       if (v == 12345)  // timing-only: drop the accumulation (never true in practice)
 #endif
-      lds_add_by_key(hkey, hval, (st.strip + (uint32_t)ip) * kQPad + (uint32_t)act, v, dbase);
+      lds_add_by_key(hkey, hval, role_off + (st.strip + (uint32_t)ip) * kQPad + (uint32_t)act, v, dbase);
     }
     if (active && (rec & 31u)) {
       if (rec & 1u) rec_reward[tA] = rw;
@@ -2372,16 +2384,16 @@ void launch_rule_g(const EpisodeParams& p, float* hp_on, hipStream_t st) {
   hipLaunchKernelGGL(rule_episode_kernel<G>, dim3((p.S + SPW - 1) / SPW), dim3(kWave), 0, st, p, hp_on);
 }
 
-template <int NC, bool WIDE, typename QT, bool SQ>
+template <int NC, bool WIDE, typename QT, bool SQ, bool ROLE = false>
 void launch_nq(const EpisodeParams& p, hipStream_t st) {
   constexpr int SPW = kWave / pow2ceil(NC);
   constexpr int WPB = general_wpb<NC, WIDE, SQ>();
   const int waves = (p.S + SPW - 1) / SPW;
   const int blocks = (waves + WPB - 1) / WPB;
   if (p.nt == 20 && p.nT == 20 && p.nb == 20 && p.np == 20)
-    hipLaunchKernelGGL((episode_kernel<NC, WIDE, QT, true, SQ>), dim3(blocks), dim3(kWave * WPB), 0, st, p);
+    hipLaunchKernelGGL((episode_kernel<NC, WIDE, QT, true, SQ, ROLE>), dim3(blocks), dim3(kWave * WPB), 0, st, p);
   else
-    hipLaunchKernelGGL((episode_kernel<NC, WIDE, QT, false, SQ>), dim3(blocks), dim3(kWave * WPB), 0, st, p);
+    hipLaunchKernelGGL((episode_kernel<NC, WIDE, QT, false, SQ, ROLE>), dim3(blocks), dim3(kWave * WPB), 0, st, p);
 }
 
 template <int NC, bool WIDE, typename QT>
@@ -2403,6 +2415,21 @@ template <int NC>
 hipError_t launch_wide(const EpisodeParams& p, int q_dtype, hipStream_t st) {
   if (p.N < 1 || p.N > NC) return hipErrorInvalidValue;
   return q_dtype == 0 ? launch_n<NC, true, double>(p, st) : launch_n<NC, true, float>(p, st);
+}
+
+// per-role tables (shared_q = 2): the shared-table form with a table per agent position
+template <int N>
+hipError_t launch_role_nd(const EpisodeParams& p, int q_dtype, hipStream_t st) {
+  if (q_dtype == 0) launch_nq<N, false, double, true, true>(p, st);
+  else launch_nq<N, false, float, true, true>(p, st);
+  return hipGetLastError();
+}
+template <int NC>
+hipError_t launch_role_wide(const EpisodeParams& p, int q_dtype, hipStream_t st) {
+  if (p.N < 1 || p.N > NC) return hipErrorInvalidValue;
+  if (q_dtype == 0) launch_nq<NC, true, double, true, true>(p, st);
+  else launch_nq<NC, true, float, true, true>(p, st);
+  return hipGetLastError();
 }
 
 // ----------------------------------------------------------------- small kernels
@@ -2773,11 +2800,54 @@ hipError_t launch_tile_part10(const EpisodeParams& p, int q_dtype, int nc, hipSt
                                                                    : hipErrorInvalidValue;
 }
 #endif
+#if P2PMG_IN_PART(11)
+hipError_t launch_role_part11(const EpisodeParams& p, int q_dtype, hipStream_t stream) {
+  switch (p.N) {
+    case 1: return launch_role_nd<1>(p, q_dtype, stream);
+    case 2: return launch_role_nd<2>(p, q_dtype, stream);
+    case 3: return launch_role_nd<3>(p, q_dtype, stream);
+    case 4: return launch_role_nd<4>(p, q_dtype, stream);
+    default: return hipErrorInvalidValue;
+  }
+}
+#endif
+#if P2PMG_IN_PART(12)
+hipError_t launch_role_part12(const EpisodeParams& p, int q_dtype, hipStream_t stream) {
+  switch (p.N) {
+    case 5: return launch_role_nd<5>(p, q_dtype, stream);
+    case 6: return launch_role_nd<6>(p, q_dtype, stream);
+    case 7: return launch_role_nd<7>(p, q_dtype, stream);
+    case 8: return launch_role_nd<8>(p, q_dtype, stream);
+    default: return hipErrorInvalidValue;
+  }
+}
+#endif
+#if P2PMG_IN_PART(13)
+hipError_t launch_role_part13(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream) {
+  if (nc == 0) return p.N == 16 ? launch_role_nd<16>(p, q_dtype, stream) : hipErrorInvalidValue;
+  return nc == 16 ? launch_role_wide<16>(p, q_dtype, stream) : hipErrorInvalidValue;
+}
+#endif
+#if P2PMG_IN_PART(14)
+hipError_t launch_role_part14(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream) {
+  return nc == 32 ? launch_role_wide<32>(p, q_dtype, stream) : nc == 64 ? launch_role_wide<64>(p, q_dtype, stream)
+                                                                        : hipErrorInvalidValue;
+}
+#endif
 #if P2PMG_IN_PART(0)
 // the general kernel: registers for N in {1..8, 16}, LDS tiles for every other N <= 64 (and for any
 // N <= 64 when tile != 0, the cross-check of the two forms)
 hipError_t launch_episode(const EpisodeParams& p, int q_dtype, int tile, hipStream_t stream) {
   if (p.N < 1 || p.N > kMaxAgents) return hipErrorInvalidValue;
+  if (p.shared_q == 2) {  // per-role tables
+    if (!tile) {
+      if (p.N <= 4) return launch_role_part11(p, q_dtype, stream);
+      if (p.N <= 8) return launch_role_part12(p, q_dtype, stream);
+      if (p.N == 16) return launch_role_part13(p, q_dtype, 0, stream);
+    }
+    const int nc = general_tile_cap(p.N);
+    return nc == 16 ? launch_role_part13(p, q_dtype, nc, stream) : launch_role_part14(p, q_dtype, nc, stream);
+  }
   if (!tile) {
     if (p.N <= 4) return launch_general_part6(p, q_dtype, stream);
     if (p.N <= 8) return launch_general_part7(p, q_dtype, stream);

@@ -98,7 +98,10 @@ struct p2pmg_ctx {
   bool prof_bounded = false; // every |load|, |pv| <= 2^100 and finite (set_profiles)
   bool hp_bounded = true;    // every heat-pump level |x| <= 2^100 and finite (defaults: 0 .. 3 kW)
   double bat_min = 0.1, bat_max = 0.9, bat_sqrt_eff = 1.0;
-  long long* qdelta = nullptr; // shared table deltas [kDeltaCopies][n_states][4]
+  size_t n_tables = 0;         // Q-tables held: A (shared_q = 0), 1 (1), N (P2PMG_SHARED_ROLE); 0 with the DQN learner
+  bool roles = false;          // cfg.shared_q == P2PMG_SHARED_ROLE
+  long long* qdelta = nullptr; // shared table deltas [kDeltaCopies][n_tables][n_states][4]
+  size_t delta_n() const { return n_tables * n_states * kQPad; }  // entries of one delta replica
   void* comm = nullptr;        // ncclComm_t
   int rank = 0, nranks = 1;    // this context's rank and the world (RCCL communicator or DQN host exchange)
   p2pmg_exchange_fn xfn = nullptr;  // DQN shared network: host gather of the gradient segments
@@ -280,9 +283,13 @@ int p2pmg_config_default(p2pmg_config* cfg) {
   return P2PMG_OK;
 }
 
+// why the calling thread's last p2pmg_create failed, where it says (no context exists to hold it)
+static thread_local std::string create_err;
+
 int p2pmg_create(const p2pmg_config* cfg, int device, p2pmg_ctx** out) {
   if (!cfg || !out) return P2PMG_E_INVALID;
   *out = nullptr;
+  create_err.clear();
   if (cfg->n_scenarios <= 0 || cfg->n_agents <= 0 || cfg->rounds < 0 || cfg->horizon <= 0) return P2PMG_E_INVALID;
   if (cfg->rounds + 1 > p2pmg::kMaxRounds1) return P2PMG_E_UNSUPPORTED;
   if (cfg->n_actions != 3) return P2PMG_E_UNSUPPORTED;
@@ -290,6 +297,10 @@ int p2pmg_create(const p2pmg_config* cfg, int device, p2pmg_ctx** out) {
   // any community size a scenario's wave holds (get_community takes any n_agents, community.py:198-204)
   if (N > p2pmg::kMaxAgents) return P2PMG_E_UNSUPPORTED;
   if (cfg->q_dtype != P2PMG_Q_F64 && cfg->q_dtype != P2PMG_Q_F32) return P2PMG_E_INVALID;
+  if (cfg->shared_q == P2PMG_SHARED_ROLE && cfg->learner == P2PMG_LEARNER_DQN) {
+    create_err = "create: shared_q = P2PMG_SHARED_ROLE needs learner = TABULAR (a Q-network per role is not built)";
+    return P2PMG_E_UNSUPPORTED;
+  }
   p2pmg_ctx* c = new (std::nothrow) p2pmg_ctx();
   if (!c) return P2PMG_E_NOMEM;
   c->cfg = *cfg;
@@ -324,12 +335,13 @@ int p2pmg_create(const p2pmg_config* cfg, int device, p2pmg_ctx** out) {
   if (hipMemsetAsync(c->codes, 0xFF, ncw * 4, c->stream) != hipSuccess) return bail(P2PMG_E_HIP);
   if (cfg->learner != P2PMG_LEARNER_TABULAR && cfg->learner != P2PMG_LEARNER_DQN) return bail(P2PMG_E_INVALID);
   c->dqn = cfg->learner == P2PMG_LEARNER_DQN;
-  const size_t n_tables = c->dqn ? 0 : (cfg->shared_q ? 1 : A);
-  const size_t qbytes = n_tables * c->n_states * kQPad * c->q_elem;
+  c->roles = cfg->shared_q == P2PMG_SHARED_ROLE;
+  c->n_tables = c->dqn ? 0 : (c->roles ? (size_t)N : cfg->shared_q ? 1 : A);
+  const size_t qbytes = c->n_tables * c->n_states * kQPad * c->q_elem;
   if (hipMalloc(&c->q, qbytes ? qbytes : 16) != hipSuccess) return bail(P2PMG_E_NOMEM);
   if (cfg->shared_q && !c->dqn) {
-    if (dmalloc(&c->qdelta, p2pmg::kDeltaCopies * c->n_states * kQPad) != hipSuccess) return bail(P2PMG_E_NOMEM);
-    if (hipMemsetAsync(c->qdelta, 0, p2pmg::kDeltaCopies * c->n_states * kQPad * 8, c->stream) != hipSuccess)
+    if (dmalloc(&c->qdelta, p2pmg::kDeltaCopies * c->delta_n()) != hipSuccess) return bail(P2PMG_E_NOMEM);
+    if (hipMemsetAsync(c->qdelta, 0, p2pmg::kDeltaCopies * c->delta_n() * 8, c->stream) != hipSuccess)
       return bail(P2PMG_E_HIP);
   }
   if (dmalloc(&c->hp_lv, A) != hipSuccess || dmalloc(&c->soc, A) != hipSuccess || dmalloc(&c->thermal, A) != hipSuccess)
@@ -419,7 +431,10 @@ int p2pmg_destroy(p2pmg_ctx* c) {
   return P2PMG_OK;
 }
 
-const char* p2pmg_last_error(const p2pmg_ctx* c) { return c ? c->err.c_str() : "null context"; }
+const char* p2pmg_last_error(const p2pmg_ctx* c) {
+  if (c) return c->err.c_str();
+  return create_err.empty() ? "null context" : create_err.c_str();
+}
 
 int p2pmg_sync(p2pmg_ctx* c) {
   if (!c) return P2PMG_E_INVALID;
@@ -556,15 +571,14 @@ int p2pmg_set_replay_codes(p2pmg_ctx* c, const uint8_t* codes) {
 int p2pmg_zero_q(p2pmg_ctx* c) {
   if (!c) return P2PMG_E_INVALID;
   if (c->dqn) return fail(c, P2PMG_E_STATE, "zero_q: DQN context has no Q-table");
-  const size_t n_tables = c->cfg.shared_q ? 1 : (size_t)c->A;
-  HIP_TRY(c, hipMemsetAsync(c->q, 0, n_tables * c->n_states * kQPad * c->q_elem, c->stream));
-  if (c->qdelta) HIP_TRY(c, hipMemsetAsync(c->qdelta, 0, p2pmg::kDeltaCopies * c->n_states * kQPad * 8, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->q, 0, c->n_tables * c->n_states * kQPad * c->q_elem, c->stream));
+  if (c->qdelta) HIP_TRY(c, hipMemsetAsync(c->qdelta, 0, p2pmg::kDeltaCopies * c->delta_n() * 8, c->stream));
   return P2PMG_OK;
 }
 
 static int q_range_ok(p2pmg_ctx* c, int first, int count, const void* host, int dtype) {
   if (c && c->dqn) return 0;
-  const int n_tables = c && c->cfg.shared_q ? 1 : (c ? c->A : 0);
+  const int n_tables = c ? (int)c->n_tables : 0;
   if (!c || !host || first < 0 || count < 0 || first + count > n_tables) return 0;
   return dtype == P2PMG_Q_F64 || dtype == P2PMG_Q_F32;
 }
@@ -635,7 +649,7 @@ static EpisodeParams episode_params(p2pmg_ctx* c, const p2pmg_episode_args* args
   p.rec_action = c->rec_action;
   p.rec_index = c->rec_index;
   p.ep_reward = c->ep_reward;
-  p.shared_q = g.shared_q ? 1 : 0;
+  p.shared_q = c->roles ? 2 : g.shared_q ? 1 : 0;
   p.qdelta = c->qdelta;
   p.battery = c->battery ? 1 : 0;
   p.bat_safe = (c->battery && c->bat_domain && c->prof_bounded && c->hp_bounded) ? 1 : 0;
@@ -734,7 +748,7 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
   if (ch && !(fast && train && args->rng == P2PMG_RNG_PHILOX))
     return fail(c, P2PMG_E_INVALID, "run_episode: a chained launch needs the fast kernel and Philox training");
   // shared table, 16-agent scenarios (configs[2]): episode_sq16_kernel
-  const bool sq16 = g.shared_q && c->N == 16 && c->R <= 1 && c->mi_ok && host_div_range(g.minutes_per_hour) &&
+  const bool sq16 = g.shared_q && !c->roles && c->N == 16 && c->R <= 1 && c->mi_ok && host_div_range(g.minutes_per_hour) &&
                     (long long)c->T * c->A < (1LL << 32) && (long long)c->T * c->n_env * p2pmg::kEnvStride < (1LL << 32) &&
                     host_div_range(g.temp_margin) && g.n_time_states == 20 && g.n_temp_states == 20 &&
                     g.n_balance_states == 20 && g.n_p2p_states == 20 &&
@@ -888,7 +902,7 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
   c->last_kernel = std::string(fast ? "episode_fast_kernel<" : sq16 ? "episode_sq16_kernel<" : "episode_kernel<") +
                    std::to_string(c->N) + (tile ? ",tile" + std::to_string(p2pmg::general_tile_cap(c->N)) : "") + "," +
                    (g.q_dtype == 0 ? "f64" : "f32") + ",R1=" + std::to_string(c->R + 1) +
-                   (ext ? (train ? ",train" : ",greedy") : "") + (g.shared_q ? ",shared" : "") +
+                   (ext ? (train ? ",train" : ",greedy") : "") + (g.shared_q ? ",shared" : "") + (c->roles ? ",roles" : "") +
                    (c->battery ? (ext && !p.bat_safe ? ",battery,range-checked>" : ",battery>") : ">");
   if (!ext && stamp) HIP_TRY(c, hipEventRecord(r1, c->stream));
   if (fast) c->pslot ^= 1;
@@ -1353,8 +1367,8 @@ int p2pmg_battery_seq(p2pmg_ctx* c, int agents, int steps, const double* bal, do
 int p2pmg_apply_q_delta(p2pmg_ctx* c) {
   if (!c) return P2PMG_E_INVALID;
   if (!c->qdelta) return fail(c, P2PMG_E_STATE, "apply_q_delta: context has no shared table");
-  HIP_TRY(c, p2pmg::launch_fold_delta(c->qdelta, c->n_states * kQPad, c->stream));
-  HIP_TRY(c, p2pmg::launch_apply_delta(c->q, c->qdelta, c->n_states * kQPad, c->cfg.q_dtype, c->stream));
+  HIP_TRY(c, p2pmg::launch_fold_delta(c->qdelta, c->delta_n(), c->stream));
+  HIP_TRY(c, p2pmg::launch_apply_delta(c->q, c->qdelta, c->delta_n(), c->cfg.q_dtype, c->stream));
   return P2PMG_OK;
 }
 
@@ -1362,11 +1376,11 @@ int p2pmg_get_q_delta(p2pmg_ctx* c, int64_t* host) {
   if (!c || !host) return P2PMG_E_INVALID;
   if (!c->qdelta) return fail(c, P2PMG_E_STATE, "get_q_delta: context has no shared table");
   const int na = c->cfg.n_actions;
-  std::vector<long long> h(c->n_states * kQPad);
-  HIP_TRY(c, p2pmg::launch_fold_delta(c->qdelta, c->n_states * kQPad, c->stream));
+  std::vector<long long> h(c->delta_n());
+  HIP_TRY(c, p2pmg::launch_fold_delta(c->qdelta, c->delta_n(), c->stream));
   HIP_TRY(c, hipMemcpyAsync(h.data(), c->qdelta, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t r = 0; r < c->n_states; ++r)
+  for (size_t r = 0; r < c->n_tables * c->n_states; ++r)  // rows of every table, in table order
     for (int k = 0; k < na; ++k) host[r * na + k] = h[r * kQPad + k];
   return P2PMG_OK;
 }
@@ -1375,8 +1389,8 @@ int p2pmg_set_q_delta(p2pmg_ctx* c, const int64_t* host) {
   if (!c || !host) return P2PMG_E_INVALID;
   if (!c->qdelta) return fail(c, P2PMG_E_STATE, "set_q_delta: context has no shared table");
   const int na = c->cfg.n_actions;
-  std::vector<long long> h(c->n_states * kQPad, 0);
-  for (size_t r = 0; r < c->n_states; ++r)
+  std::vector<long long> h(c->delta_n(), 0);
+  for (size_t r = 0; r < c->n_tables * c->n_states; ++r)
     for (int k = 0; k < na; ++k) h[r * kQPad + k] = host[r * na + k];
   HIP_TRY(c, hipMemsetAsync(c->qdelta, 0, p2pmg::kDeltaCopies * h.size() * 8, c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->qdelta, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
@@ -1457,9 +1471,9 @@ int p2pmg_allreduce_q_delta(p2pmg_ctx* c) {
   if (!c->comm) return fail(c, P2PMG_E_STATE, "allreduce_q_delta: p2pmg_comm_init first");
   Rccl* r = rccl();
   // ncclInt64 = 4, ncclSum = 0 (rccl.h)
-  HIP_TRY(c, p2pmg::launch_fold_delta(c->qdelta, c->n_states * kQPad, c->stream));
+  HIP_TRY(c, p2pmg::launch_fold_delta(c->qdelta, c->delta_n(), c->stream));
   HIP_TRY(c, coll_mark(c, 0));
-  const int rc = r->allReduce(c->qdelta, c->qdelta, c->n_states * kQPad, 4, 0, c->comm, c->stream);
+  const int rc = r->allReduce(c->qdelta, c->qdelta, c->delta_n(), 4, 0, c->comm, c->stream);
   if (rc != 0) return fail(c, P2PMG_E_HIP, std::string("ncclAllReduce: ") + (r->getErrorString ? r->getErrorString(rc) : "?"));
   HIP_TRY(c, coll_mark(c, 1));
   return P2PMG_OK;
@@ -1493,11 +1507,11 @@ int p2pmg_allreduce_metrics(p2pmg_ctx* c, double* out) {
 
 int p2pmg_table_hash_allgather(p2pmg_ctx* c, uint64_t* out) {
   if (!c || !out) return P2PMG_E_INVALID;
-  if (!c->q) return fail(c, P2PMG_E_STATE, "table_hash: context has no Q-table");
+  if (!c->q || c->n_tables == 0) return fail(c, P2PMG_E_STATE, "table_hash: context has no Q-table");
   const int n = c->comm ? c->nranks : 1;
   if (n > 1024) return fail(c, P2PMG_E_UNSUPPORTED, "table_hash: more than 1024 ranks");
   if (!c->d_hash) HIP_TRY(c, dmalloc(&c->d_hash, 1025));
-  const size_t bytes = (c->cfg.shared_q ? (size_t)1 : (size_t)c->A) * c->n_states * kQPad * c->q_elem;
+  const size_t bytes = c->n_tables * c->n_states * kQPad * c->q_elem;
   HIP_TRY(c, p2pmg::launch_table_hash(c->q, bytes, c->d_hash + 1024, c->stream));
   if (c->comm) {  // ncclUint64 = 5: every rank's fingerprint, in rank order
     Rccl* r = rccl();
@@ -1526,7 +1540,7 @@ int p2pmg_q_calls(p2pmg_ctx* c, int n, const int32_t* agents, const float* s_obs
   if (train && (!rewards || !ns_obs)) return fail(c, P2PMG_E_INVALID, "q_calls: train needs rewards and ns_obs");
   if (c->dqn) return fail(c, P2PMG_E_STATE, "q_calls: DQN context has no Q-table");
   for (int k = 0; k < n; ++k)
-    if (agents[k] < 0 || agents[k] >= c->A) return fail(c, P2PMG_E_INVALID, "q_calls: agent out of range");
+    if (agents[k] < 0 || (size_t)agents[k] >= c->n_tables) return fail(c, P2PMG_E_INVALID, "q_calls: agent out of range");
   if (n == 0) return P2PMG_OK;
   // one staging block: agents | s_obs | ns_obs | rewards | codes | actions | q_out
   const size_t nb = (size_t)n;

@@ -123,7 +123,10 @@ class ShardedTrainer:
     engine_factory(shard, S, N, R, T, q_dtype, device, seed, shared_q, **dqn) -> an object with the
     DeviceCommunityBatch (DeviceDQNBatch) interface; the default is the HIP engine.
 
-    shared_q: one policy table for every agent of every scenario on every rank (config 3).
+    shared_q: True = one policy table for every agent of every scenario on every rank (config 3);
+    "role" = one table per agent position, shared by that position's agents of every scenario on
+    every rank (one community of N learners over all the scenarios).  The delta exchange is the
+    same in both, over N times the buffer with "role".
     exchange: how the shared-table deltas and the episode metrics are summed over ranks — "rccl"
     (device all-reduce over xGMI through the context's RCCL communicator, the production path),
     "host" (copy out, sum over the torch process group, copy back) or "auto" (rccl when the
@@ -137,13 +140,15 @@ class ShardedTrainer:
 
     def __init__(self, n_scenarios: int, n_agents: int = 2, rounds: int = 1, horizon: int = 96,
                  q_dtype: str = "f64", seed: int = 42, rank: int = 0, world: int = 1, device: int = 0,
-                 engine_factory: Optional[Callable] = None, shared_q: bool = False, exchange: str = "auto",
+                 engine_factory: Optional[Callable] = None, shared_q=False, exchange: str = "auto",
                  battery: Optional[dict] = None, homogeneous: bool = False, learner: str = "tabular",
                  grad_segments: Optional[int] = None, agents_per_block: int = 0):
         from .dataset import scenario_batch
         if learner not in ("tabular", "dqn"):
             raise ValueError(f"learner must be 'tabular' or 'dqn', got {learner!r}")
         self.learner = learner
+        if isinstance(shared_q, str) and (shared_q != "role" or learner == "dqn"):
+            raise ValueError(f"shared_q must be False, True or (tabular learner only) 'role', got {shared_q!r}")
         dqn_kw = {}
         if learner == "dqn":
             G = world if grad_segments is None else int(grad_segments)
@@ -163,7 +168,7 @@ class ShardedTrainer:
             self.filled = False
         self.sh = shard(n_scenarios, rank, world)
         self.S_total, self.N, self.R, self.T = n_scenarios, n_agents, rounds, horizon
-        self.rank, self.world, self.shared_q = rank, world, bool(shared_q)
+        self.rank, self.world = rank, world
         inp = scenario_batch(self.sh.count, n_agents, horizon, seed=seed, first_scenario=self.sh.first,
                              homogeneous=homogeneous)
         if engine_factory is None:
@@ -176,7 +181,7 @@ class ShardedTrainer:
                 from .engine import DeviceCommunityBatch
                 return DeviceCommunityBatch(S, N, R, T, q_dtype=q_dtype, device=device, seed=seed,
                                             scenario_offset=sh.first, shared_q=shared_q)
-        self.shared_q = bool(shared_q)
+        self.shared_q = "role" if shared_q == "role" else bool(shared_q)
         self.eng = engine_factory(self.sh, self.sh.count, n_agents, rounds, horizon, q_dtype, device, seed,
                                   shared_q=self.shared_q, **dqn_kw)
         self.eng.set_env(np.broadcast_to(inp.time, inp.t_out.shape), inp.t_out)

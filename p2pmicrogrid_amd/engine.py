@@ -41,14 +41,20 @@ class DeviceCommunityBatch:
     """Device-resident batch of S communities.  All compute runs in libp2pmg.so."""
 
     def __init__(self, n_scenarios: int, n_agents: int, rounds: int, horizon: int, q_dtype: str = "f64",
-                 device: int = 0, seed: int = 42, scenario_offset: int = 0, shared_q: bool = False, **overrides):
+                 device: int = 0, seed: int = 42, scenario_offset: int = 0, shared_q=False, **overrides):
+        """shared_q: False (a table per agent of every scenario), True (one table for all) or "role"
+        (one table per agent position i, read by agent (s, i) of every scenario s: one community of N
+        learners over S scenarios; tables frozen during an episode, updated by apply_q_delta)."""
         self.L = _lib.lib()
         cfg = _lib.default_config()
         cfg.n_scenarios, cfg.n_agents, cfg.rounds, cfg.horizon = n_scenarios, n_agents, rounds, horizon
         cfg.q_dtype = _lib.Q_F64 if q_dtype == "f64" else _lib.Q_F32
         cfg.seed = seed
         cfg.scenario_offset = scenario_offset
-        cfg.shared_q = int(bool(shared_q))
+        role = isinstance(shared_q, str)
+        if role and shared_q != "role":
+            raise ValueError(f"shared_q must be False, True or 'role', got {shared_q!r}")
+        cfg.shared_q = _lib.SHARED_ROLE if role else int(bool(shared_q))
         for k, v in overrides.items():
             setattr(cfg, k, v)
         self.cfg = cfg
@@ -58,13 +64,19 @@ class DeviceCommunityBatch:
         self.device = device
         self.seed = seed
         self.scenario_offset = scenario_offset
-        self.shared_q = bool(shared_q)
-        self.n_tables = 1 if shared_q else self.A
+        self.shared_q = "role" if role else bool(shared_q)
+        self.n_tables = n_agents if role else (1 if shared_q else self.A)
         self.n_states = cfg.n_time_states * cfg.n_temp_states * cfg.n_balance_states * cfg.n_p2p_states
         self.q_shape = (cfg.n_time_states, cfg.n_temp_states, cfg.n_balance_states, cfg.n_p2p_states,
                         cfg.n_actions)
         ctx = C.c_void_p()
-        _lib.check(self.L.p2pmg_create(C.byref(cfg), device, C.byref(ctx)), what="p2pmg_create")
+        status = self.L.p2pmg_create(C.byref(cfg), device, C.byref(ctx))
+        if status != _lib.P2PMG_OK:
+            # a failed create leaves no context: where it gives a reason, that is the calling
+            # thread's p2pmg_last_error(NULL)
+            raw = self.L.p2pmg_last_error(None) or b""
+            msg = "" if raw == b"null context" else raw.decode()
+            raise _lib.P2PMGError(f"p2pmg_create: {_lib.STATUS.get(status, status)} {msg}".strip())
         self._ctx = ctx
         self._recorded = 0
 
@@ -227,12 +239,17 @@ class DeviceCommunityBatch:
         self._chk(self.L.p2pmg_apply_q_delta(self._ctx), "apply_q_delta")
 
     def get_q_delta(self):
-        out = np.empty((self.n_states, self.q_shape[-1]), np.int64)
+        """int64 fixed-point (2^-40) deltas in q_shape; with per-role tables [N, *q_shape]."""
+        if self.shared_q == "role":
+            out = np.empty((self.N, *self.q_shape), np.int64)
+        else:
+            out = np.empty(self.q_shape, np.int64)
         self._chk(self.L.p2pmg_get_q_delta(self._ctx, out.ctypes.data), "get_q_delta")
-        return out.reshape(self.q_shape)
+        return out
 
     def set_q_delta(self, delta):
-        d = np.ascontiguousarray(np.asarray(delta, np.int64).reshape(self.n_states, self.q_shape[-1]))
+        rows = self.n_states * (self.N if self.shared_q == "role" else 1)
+        d = np.ascontiguousarray(np.asarray(delta, np.int64).reshape(rows, self.q_shape[-1]))
         self._chk(self.L.p2pmg_set_q_delta(self._ctx, d.ctypes.data), "set_q_delta")
 
     def comm_init(self, unique_id: bytes, rank: int, nranks: int):
