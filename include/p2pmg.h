@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels */
+#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary) */
 
 typedef struct p2pmg_ctx p2pmg_ctx;
 
@@ -223,6 +223,49 @@ int p2pmg_run_episodes(p2pmg_ctx* ctx, const p2pmg_episode_args* args, int n, co
 int p2pmg_get_episode_rewards(p2pmg_ctx* ctx, int n, float* host);
 /* one P2PMG_REC_* bit of the LAST episode launch; P2PMG_E_STATE if that launch did not record it */
 int p2pmg_get_record(p2pmg_ctx* ctx, int which, void* host);
+/* Episode summary: the records of the LAST episode launch reduced over time ON THE DEVICE to
+ * P2PMG_SUMMARY_FIELDS f64 values per agent and per scenario (the totals behind the reference's
+ * figures: daily cost per agent, self-consumption, grid load; data_analysis.py:188-209, 324-420,
+ * 775-846), so that only [A][16] + [S][16] doubles are copied to the host instead of the per-step
+ * records.  A post-pass over what the launch wrote: that launch must have recorded every bit of
+ * P2PMG_SUMMARY_RECORDS (else P2PMG_E_STATE, p2pmg_last_error names what is missing; the fast and
+ * sq16 kernels' narrow reward + cost form and "no episode yet" included).  P2PMG_REC_REWARD is
+ * optional: without it field 1 is 0 (rule episodes never record it).  After p2pmg_run_episodes it
+ * describes the last episode of the chain, whose records remain.  load and pv are read from the
+ * context's profile buffer, hp levels and comfort bounds from the per-agent arrays, as they are at
+ * the call.  Stream-ordered, synchronises before returning (like p2pmg_get_record).
+ *
+ * Per agent a = s N + i, every field accumulated in f64 SEQUENTIALLY over t = 0..T-1 from +0.0, each
+ * term formed in f32 as written and then widened (max(x, 0) is x > 0 ? x : +0); this order is the
+ * definition:
+ *    0 cost              cost[t,a]                                         (currency of the prices)
+ *    1 reward            reward[t,a]
+ *    2 grid_import       max(grid[t,a], 0)                                 W-steps
+ *    3 grid_export       max(-grid[t,a], 0)
+ *    4 p2p_import        max(p2p[t,a], 0)
+ *    5 p2p_export        max(-p2p[t,a], 0)
+ *    6 hp                hp_levels[a][action[t,R,a]]: the final round's action, the power the RC step used
+ *    7 load              load_w[a][t]
+ *    8 pv                pv_w[a][t]
+ *    9 self_consumption  power = grid + p2p (one f32 add, what run() returns); power < 0 ? pv + power : pv
+ *                        (data_analysis.py:195)
+ *   10 discomfort_deg    d = max(max(0, lower_a - T_in), max(0, T_in - upper_a)), T_in before the step's
+ *                        RC update, the agent's own bounds (p2pmg_set_thermal)
+ *   11 discomfort_steps  d > 0 ? 1 : 0
+ *   12 t_in_min          running minimum of T_in (not a sum)
+ *   13 t_in_max          running maximum of T_in
+ *   14 peak_import       running maximum of max(grid, 0), W
+ *   15 peak_export       running maximum of max(-grid, 0)
+ * The comfort penalty of the reward (agent.py:225-232) summed over the episode is
+ * penalty_weight * (field 10 + field 11).
+ * Per scenario s: fields 0-11 are the sequential f64 sum over i = 0..N-1 of the agents' values, 12 the
+ * minimum and 13 the maximum over the agents' 12 and 13, 14 and 15 the COMMUNITY's peaks
+ * max_t max(G_t, 0) and max_t max(-G_t, 0), G_t the sequential f32 sum over i of grid[t, s N + i] from
+ * +0.0: the net load the community puts on the grid (plot_grid_load). */
+#define P2PMG_SUMMARY_FIELDS 16
+#define P2PMG_SUMMARY_RECORDS (P2PMG_REC_COST | P2PMG_REC_GRID | P2PMG_REC_P2P | P2PMG_REC_TEMP | P2PMG_REC_ACTION)
+/* per_agent [A][16] f64 and/or per_scenario [S][16] f64 (either may be NULL, not both) */
+int p2pmg_episode_summary(p2pmg_ctx* ctx, double* per_agent, double* per_scenario);
 /* fast path: episode launches whose step pre-pass the previous launch had already produced (hits)
  * and launches that had to run it themselves (misses), since the context was created */
 int p2pmg_prepass_stats(p2pmg_ctx* ctx, int64_t* hits, int64_t* misses);

@@ -43,6 +43,7 @@ EXPORTS = [
     "p2pmg_allreduce_metrics", "p2pmg_table_hash_allgather", "p2pmg_dqn_set_exchange", "p2pmg_dqn_grad_layout",
     "p2pmg_run_episodes", "p2pmg_get_episode_rewards",
     "p2pmg_set_thermal", "p2pmg_get_thermal", "p2pmg_rc_step_ex", "p2pmg_get_hp_levels",
+    "p2pmg_episode_summary",
 ]
 
 
@@ -120,6 +121,7 @@ def _declare(lib):
         "p2pmg_get_episode_rewards": ([vp, i32, fp], i32),
         "p2pmg_get_record": ([vp, i32, vp], i32),
         "p2pmg_get_episode_reward": ([vp, fp], i32),
+        "p2pmg_episode_summary": ([vp, vp, vp], i32),
         "p2pmg_last_kernel_ms": ([vp, C.POINTER(C.c_float)], i32),
         "p2pmg_rc_step": ([vp, i32, fp, fp, fp, fp, fp, fp], i32),
         "p2pmg_rc_step_ex": ([vp, i32, fp, fp, fp, fp, vp, C.c_float, fp, fp], i32),

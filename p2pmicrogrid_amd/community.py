@@ -242,7 +242,15 @@ class CommunityMicrogrid:
         power = (r["grid"][:, 0, :] + r["p2p"][:, 0, :]).astype(F32)
         return power, r["cost"][:, 0, :]
 
-    def run_days(self, days) -> List[Dict[str, np.ndarray]]:
+    def summary(self, kwh: bool = False) -> Dict[str, np.ndarray]:
+        """After run(): the episode's totals per agent, {name: [N] f64} for engine.SUMMARY_FIELDS (cost,
+        grid and peer energy, self-consumption, discomfort, peaks), reduced on the device from the
+        records run() left there (DeviceCommunityBatch.episode_summary)."""
+        if self._engine is None:
+            raise RuntimeError("summary() describes the last run(): call run() first")
+        return {k: v[0] for k, v in self._engine.episode_summary(kwh=kwh)["agent"].items()}
+
+    def run_days(self, days, summary: bool = False) -> List[Dict[str, np.ndarray]]:
         """run() of this community over several days in ONE greedy launch: a per-role-table engine
         (``shared_q="role"``) with one scenario per day, holding one copy of every agent's table
         instead of one per day.  ``days``: a sequence of dicts {"time" [T], "t_out" [T], "load" [N, T],
@@ -250,6 +258,8 @@ class CommunityMicrogrid:
         "cost" [T, N] and "decisions" [T, R + 1, N] as run() gives them, plus "t_in" [T, N] (T_in before
         each step) and "t_in_final" / "t_m_final" [N].  Each day is bit for bit what run() computes
         from that day's inputs.  The agents' tables are read, nothing else of the community changes.
+        ``summary=True`` adds "summary": {name: [N] f64} per day, the day's totals per agent
+        (engine.SUMMARY_FIELDS) from one device-side reduction of the launch's records.
         Tabular communities only."""
         if self._rule or self._dqn:
             raise NotImplementedError("run_days needs tabular (QAgent) agents: per-role tables hold Q-tables, "
@@ -279,6 +289,7 @@ class CommunityMicrogrid:
             eng.run_episode("greedy", record=rec)
             r = eng.get_records(rec)
             t_in, t_m = eng.get_temperatures()
+            totals = eng.episode_summary()["agent"] if summary else None
         finally:
             eng.close()
         max_power = np.array([a.heating.hp.max_power for a in self.agents])
@@ -287,6 +298,8 @@ class CommunityMicrogrid:
             out.append({"power": (r["grid"][:, d, :] + r["p2p"][:, d, :]).astype(F32), "cost": r["cost"][:, d, :],
                         "decisions": np.array(ACTION_LEVELS)[r["action"][:, :, d, :]] * max_power[None, None, :],
                         "t_in": r["t_in"][:, d, :], "t_in_final": t_in[d], "t_m_final": t_m[d]})
+            if totals is not None:
+                out[-1]["summary"] = {k: v[d] for k, v in totals.items()}
         return out
 
     def _run_rule(self) -> Tuple[np.ndarray, np.ndarray]:

@@ -217,6 +217,27 @@ constexpr int kFastBatMaxR1 = 2;      // episode_fast_kernel's battery variants:
 // which: 0..4 reward, cost, grid, p2p, tin ([T][A] f32); 5 action (u8), 6 index (i32) [T][R+1][A]
 hipError_t launch_fast_rec_unpack(int T, int R1, int A, uint32_t tb, const void* recs, int narrow, int which, void* out,
                                   hipStream_t stream);
+// p2pmg_episode_summary (p2pmg_summary.hip): the last launch's records reduced over time
+constexpr int kSummaryFields = 16;  // P2PMG_SUMMARY_FIELDS
+struct SummaryParams {
+  int S, N, R, T, A;
+  int packed;                 // 1: the records are rec_pack's 32-B rows (fast / sq16 launches), else the plain arrays
+  int has_reward;             // 0: the launch recorded no reward (field 1 = 0)
+  const float* cost;          // [T][A] plain arrays (packed = 0)
+  const float* reward;
+  const float* grid;
+  const float* p2p;
+  const float* tin;
+  const uint8_t* action;      // [T][R+1][A]
+  const void* rec_pack;       // [T][A] x kFastRecBytes (packed = 1)
+  const float2* prof;         // [T][A] {load_w, pv_w}
+  const float4* hp_lv;        // [A]
+  const float4* thermal;      // [A] {setpoint, lower bound, upper bound, COP}
+  double* agent_out;          // [A][kSummaryFields]
+  double* scen_out;           // [S][kSummaryFields]
+};
+// summary_agent_kernel then summary_scenario_kernel (which reads agent_out) on the stream
+hipError_t launch_episode_summary(const SummaryParams& p, hipStream_t stream);
 hipError_t launch_apply_delta(void* q, long long* qdelta, size_t n, int q_dtype, hipStream_t stream);
 hipError_t launch_fold_delta(long long* qdelta, size_t n, hipStream_t stream);
 hipError_t launch_battery_seq(int agents, int steps, const double* bal, double* out_bal, double* soc_hist,

@@ -86,6 +86,8 @@ struct p2pmg_ctx {
   int32_t* rec_index = nullptr;
   void* rec_stage = nullptr;  // fast / sq16 launches: one staging buffer the packed rows unpack into
   size_t rec_stage_bytes = 0;
+  double* sum_agent = nullptr;  // p2pmg_episode_summary: [A][16] and [S][16], allocated on first use
+  double* sum_scen = nullptr;
   float4* hp_lv = nullptr;     // [A] per-agent heat-pump levels
   float4* thermal = nullptr;   // [A] per-agent {setpoint, lower bound, upper bound, COP} (p2pmg_set_thermal)
   bool thermal_set = false;    // p2pmg_set_thermal uploaded values (false: the config's, where sq16 applies)
@@ -395,6 +397,8 @@ int p2pmg_destroy(p2pmg_ctx* c) {
   dfree(c->rec_action);
   dfree(c->rec_index);
   if (c->rec_stage) (void)hipFree(c->rec_stage);
+  dfree(c->sum_agent);
+  dfree(c->sum_scen);
   dfree(c->hp_lv);
   dfree(c->thermal);
   dfree(c->hp_on);
@@ -1116,6 +1120,58 @@ int p2pmg_get_record(p2pmg_ctx* c, int which, void* host) {
   }
   if (!src) return fail(c, P2PMG_E_STATE, "get_record: no record buffer");
   HIP_TRY(c, hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return P2PMG_OK;
+}
+
+int p2pmg_episode_summary(p2pmg_ctx* c, double* per_agent, double* per_scenario) {
+  if (!c) return P2PMG_E_INVALID;
+  if (!per_agent && !per_scenario) return fail(c, P2PMG_E_INVALID, "episode_summary: both outputs are null");
+  if (c->last_kernel.empty()) return fail(c, P2PMG_E_STATE, "episode_summary: no episode has run (cost, grid, p2p, t_in and action records are needed)");
+  const int missing = P2PMG_SUMMARY_RECORDS & ~c->rec_last_mask;
+  if (missing) {
+    static const struct { int bit; const char* name; } names[] = {{P2PMG_REC_COST, "cost"}, {P2PMG_REC_GRID, "grid"},
+                                                                  {P2PMG_REC_P2P, "p2p"}, {P2PMG_REC_TEMP, "t_in"},
+                                                                  {P2PMG_REC_ACTION, "action"}};
+    std::string list;
+    for (const auto& n : names)
+      if (missing & n.bit) list += (list.empty() ? "" : ", ") + std::string(n.name);
+    return fail(c, P2PMG_E_STATE, "episode_summary: the last episode launch did not record " + list);
+  }
+  const size_t A = (size_t)c->A, S = (size_t)c->S;
+  if (!c->sum_agent) HIP_TRY(c, dmalloc(&c->sum_agent, A * P2PMG_SUMMARY_FIELDS));
+  if (!c->sum_scen) HIP_TRY(c, dmalloc(&c->sum_scen, S * P2PMG_SUMMARY_FIELDS));
+  p2pmg::SummaryParams p{};
+  p.S = c->S;
+  p.N = c->N;
+  p.R = c->R;
+  p.T = c->T;
+  p.A = c->A;
+  // a fast / sq16 launch packs every record it was asked for into rec_pack's rows (all of them here:
+  // the narrow {reward, cost} form lacks the records checked above)
+  p.packed = (c->rec_fast_mask & P2PMG_SUMMARY_RECORDS) ? 1 : 0;
+  p.has_reward = (c->rec_last_mask & P2PMG_REC_REWARD) ? 1 : 0;
+  p.reward = c->rec_f32[0];
+  p.cost = c->rec_f32[1];
+  p.grid = c->rec_f32[2];
+  p.p2p = c->rec_f32[3];
+  p.tin = c->rec_f32[4];
+  p.action = c->rec_action;
+  p.rec_pack = c->rec_pack;
+  p.prof = c->prof;
+  p.hp_lv = c->hp_lv;
+  p.thermal = c->thermal;
+  p.agent_out = c->sum_agent;
+  p.scen_out = c->sum_scen;
+  if (p.packed ? !p.rec_pack : (!p.cost || !p.grid || !p.p2p || !p.tin || !p.action || (p.has_reward && !p.reward)))
+    return fail(c, P2PMG_E_STATE, "episode_summary: no record buffer");
+  HIP_TRY(c, p2pmg::launch_episode_summary(p, c->stream));
+  if (per_agent)
+    HIP_TRY(c, hipMemcpyAsync(per_agent, c->sum_agent, A * P2PMG_SUMMARY_FIELDS * sizeof(double), hipMemcpyDeviceToHost,
+                              c->stream));
+  if (per_scenario)
+    HIP_TRY(c, hipMemcpyAsync(per_scenario, c->sum_scen, S * P2PMG_SUMMARY_FIELDS * sizeof(double),
+                              hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return P2PMG_OK;
 }

@@ -18,6 +18,11 @@ from . import setup as cfgmod
 
 F32 = np.float32
 RECORD_NAMES = ("reward", "cost", "grid", "p2p", "t_in", "action", "index")
+# p2pmg_episode_summary (include/p2pmg.h): the 16 fields in order, and what a launch must record for it
+SUMMARY_FIELDS = ("cost", "reward", "grid_import", "grid_export", "p2p_import", "p2p_export", "hp", "load", "pv",
+                  "self_consumption", "discomfort_deg", "discomfort_steps", "t_in_min", "t_in_max", "peak_import",
+                  "peak_export")
+SUMMARY_RECORDS = ("cost", "grid", "p2p", "t_in", "action")  # "reward" is optional (absent: field 1 is 0)
 
 
 def price_table(time_f32, grid_cost_avg=cfgmod.GRID_COST_AVG, amplitude=cfgmod.GRID_COST_AMPLITUDE,
@@ -411,6 +416,23 @@ class DeviceCommunityBatch:
 
     def get_records(self, names: Sequence[str]) -> Dict[str, np.ndarray]:
         return {n: self.get_record(n) for n in names}
+
+    def episode_summary(self, kwh: bool = False) -> Dict[str, Dict[str, np.ndarray]]:
+        """The last episode launch's records reduced over time on the device (p2pmg_episode_summary):
+        {"agent": {name: [S, N] f64}, "scenario": {name: [S] f64}} for the names in SUMMARY_FIELDS.
+        The launch must have recorded SUMMARY_RECORDS.  Energies (fields 2-9) are in W-steps;
+        kwh=True multiplies them by time_slot / 60 * 1e-3.  The peaks stay in W."""
+        nf = len(SUMMARY_FIELDS)
+        ag = np.empty((self.A, nf), np.float64)
+        sc = np.empty((self.S, nf), np.float64)
+        self._chk(self.L.p2pmg_episode_summary(self._ctx, ag.ctypes.data, sc.ctypes.data), "episode_summary")
+        if kwh:
+            k = float(self.cfg.time_slot) / 60.0 * 1e-3
+            ag[:, 2:10] *= k
+            sc[:, 2:10] *= k
+        ag = ag.reshape(self.S, self.N, nf)
+        return {"agent": {n: np.ascontiguousarray(ag[..., j]) for j, n in enumerate(SUMMARY_FIELDS)},
+                "scenario": {n: np.ascontiguousarray(sc[:, j]) for j, n in enumerate(SUMMARY_FIELDS)}}
 
     def episode_reward(self) -> np.ndarray:
         out = np.empty(self.S, F32)
