@@ -17,8 +17,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libp2pmg.so")
-SOURCES = ["p2pmg_kernels.hip", "p2pmg_dqn.hip", "p2pmg_summary.hip", "p2pmg_runtime.cpp"]
-HEADERS = ["p2pmg_internal.h", "p2pmg_device.h", os.path.join(ROOT, "include", "p2pmg.h")]
+SOURCES = ["p2pmg_kernels.hip", "p2pmg_dqn.hip", "p2pmg_summary.hip", "p2pmg_runtime.cpp", "p2pmg_plan.cpp"]
+HEADERS = ["p2pmg_internal.h", "p2pmg_device.h", "p2pmg_plan.h", os.path.join(ROOT, "include", "p2pmg.h")]
 ARCH = os.environ.get("P2PMG_ARCH", "gfx950")
 
 
@@ -51,7 +51,8 @@ PART_FLAGS = {5: ["-fno-slp-vectorize"]}
 def build(force: bool = False, verbose: bool = True, out: str = LIB, defines=(), jobs: int = 0) -> str:
     """defines: extra -D flags, or raw compiler flags when they start with "-" (timing-only ablation
     builds go to a different ``out``).
-    The translation units (15 parts of p2pmg_kernels.hip, p2pmg_dqn.hip, p2pmg_summary.hip, p2pmg_runtime.cpp) compile
+    The translation units (15 parts of p2pmg_kernels.hip, p2pmg_dqn.hip, p2pmg_summary.hip, p2pmg_runtime.cpp,
+    p2pmg_plan.cpp) compile
     in parallel into build/obj/<tag>/, then link into one shared library.  An exclusive file lock
     per tag serialises concurrent builders (torchrun ranks, pytest-xdist workers that all find the
     sources newer): the later ones wait, see a fresh library and return without compiling."""

@@ -18,132 +18,188 @@
 #include <vector>
 
 #include "p2pmg_internal.h"
+#include "p2pmg_plan.h"
 
 using p2pmg::EpisodeParams;
+using p2pmg::EpisodePlan;
+using p2pmg::Family;
 using p2pmg::kEnvStride;
 using p2pmg::kQPad;
 
-struct p2pmg_ctx {
-  p2pmg_config cfg{};
+// A device (or pinned host) array its holder owns: freed with the holder, move-only.
+template <typename T, bool Pinned = false>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept {  // o takes what this held, and frees it
+    return std::swap(p_, o.p_), std::swap(cap_, o.cap_), *this;
+  }
+  ~DevBuf() { release(); }
+  void release() {
+    if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+    p_ = nullptr, cap_ = 0;
+  }
+  // n elements (at least 16 bytes); what it held is freed first, and a failure leaves {null, 0}
+  hipError_t alloc(size_t n) {
+    release();
+    const size_t bytes = n * sizeof(T) > 0 ? n * sizeof(T) : 16;
+    const hipError_t e = Pinned ? hipHostMalloc(reinterpret_cast<void**>(&p_), bytes, hipHostMallocDefault)
+                                : hipMalloc(reinterpret_cast<void**>(&p_), bytes);
+    if (e == hipSuccess) cap_ = n;
+    else p_ = nullptr;
+    return e;
+  }
+  // at least n elements: kept when it already holds them, else reallocated (contents lost)
+  hipError_t grow(size_t n) { return p_ && cap_ >= n ? hipSuccess : alloc(n); }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+  size_t cap() const { return cap_; }
+
+ private:
+  T* p_ = nullptr;
+  size_t cap_ = 0;
+};
+template <typename T>
+using PinBuf = DevBuf<T, true>;
+
+// Start / stop event pairs, created on first use; the k-th timed interval uses pair k % slots.
+struct EventRing {
+  std::vector<hipEvent_t> ev;
+  ~EventRing() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t ensure(int slots) {
+    if (!ev.empty()) return hipSuccess;
+    ev.assign(2 * (size_t)slots, nullptr);
+    for (auto& e : ev) {
+      const hipError_t rc = hipEventCreate(&e);
+      if (rc != hipSuccess) return rc;
+    }
+    return hipSuccess;
+  }
+  hipEvent_t* pair(long long k) { return &ev[2 * (size_t)(k % (long long)(ev.size() / 2))]; }
+  hipError_t elapsed(long long k, float* ms) {  // waits for the interval's stop event
+    const hipError_t e = hipEventSynchronize(pair(k)[1]);
+    return e != hipSuccess ? e : hipEventElapsedTime(ms, pair(k)[0], pair(k)[1]);
+  }
+};
+
+struct Stream {
+  hipStream_t s = nullptr;
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  operator hipStream_t() const { return s; }
+};
+
+// What the last episode launch left behind (finish_launch writes it; tabular, rule and DQN alike).
+struct LastLaunch {
+  int mask = 0;         // records it wrote (p2pmg_get_record checks it)
+  int packed_mask = 0;  // ... those of them that live packed in rec_pack (fast / sq16 launches)
+  int narrow = 0;       // ... as [T][A] float2 {reward, cost} (fast / sq16 with only those two requested)
+  bool timed = false;   // a launch has run since the context was created
+  std::string kernel;
+};
+
+// Members are destroyed in reverse order: every buffer is freed before the events and the stream,
+// which are declared first (p2pmg_destroy synchronises the stream before the delete).
+struct p2pmg_ctx : p2pmg::PlanFacts {
   int device = 0;
-  int S = 0, N = 0, R = 0, T = 0, A = 0;
-  int n_cu = 256;  // compute units of the device (multiProcessorCount)
   size_t n_states = 0;
   size_t q_elem = 8;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
+  Stream stream;
   static constexpr int kRing = 4096;
-  std::vector<hipEvent_t> ring;  // 2 * kRing events: start/stop of each episode kernel
+  EventRing ring;                 // start/stop of each episode kernel
   long long n_timed = 0;          // launches recorded since the last reset
   static constexpr int kCRing = 1024;
-  std::vector<hipEvent_t> cring;  // 2 * kCRing events: start/stop of each data-path RCCL all-reduce
+  EventRing cring;                // start/stop of each data-path RCCL all-reduce
   long long n_coll = 0;           // collectives recorded since the last reset
   double coll_folded_ms = 0.0;    // durations of ring slots already reused (p2pmg_collective_ms)
   long long n_coll_folded = 0;    // collectives whose durations are in coll_folded_ms
   int timing_period = 1;          // episode launches: stamp timing events on every k-th one
   long long n_launch = 0;         // episode launches since the last reset
+  LastLaunch last;
   // device buffers
-  float* env = nullptr;
-  int n_env = 0;
-  float2* prof = nullptr;
-  uint2* sqp = nullptr;             // sq16 path: per-upload step words (launch_sq16_prep), lazily allocated
+  DevBuf<float> env;
+  DevBuf<float2> prof;
+  DevBuf<uint2> sqp;                // sq16 path: per-upload step words (launch_sq16_prep), lazily allocated
   long long sqp_version = -1;       // inputs_version they were computed for
-  float* max_in = nullptr;
-  float* t_in = nullptr;
-  float* t_m = nullptr;
-  void* q = nullptr;
-  uint32_t* codes = nullptr;  // code words [T][W][A]
+  DevBuf<float> max_in, t_in, t_m;
+  DevBuf<char> q;
+  DevBuf<uint32_t> codes;  // code words [T][W][A]
   // fast path: step pre-pass outputs, double-buffered.  Episode e's launch also computes, in extra
   // workgroups, slot (e+1)'s pre-pass for episode e + 1 at the same epsilon (it reads only inputs,
   // never Q or T); run_episode(e + 1) uses it when its arguments match (spec_*), else recomputes.
-  uint2* pre[2] = {nullptr, nullptr};        // [T][A] {balw, bins}
-  uint32_t* pre_ipc[2] = {nullptr, nullptr}; // N = 2: [T][A] round-1 bins per partner action
-  uint32_t* pcodes[2] = {nullptr, nullptr};  // Philox code words [T][W][A], one per episode of a chain
-  size_t pcodes_cap[2] = {0, 0};             // ... their capacity in words
+  DevBuf<uint2> pre[2];        // [T][A] {balw, bins}
+  DevBuf<uint32_t> pre_ipc[2]; // N = 2: [T][A] round-1 bins per partner action
+  DevBuf<uint32_t> pcodes[2];  // Philox code words [T][W][A], one per episode of a chain
   int pslot = 0;
   bool spec_valid[2] = {false, false};
   int spec_episode[2] = {0, 0};
-  std::vector<double> spec_chain[2];         // the epsilons of the chain a slot holds (one: {eps})
-  float* chain_rew = nullptr;                // p2pmg_run_episodes: [n][S] episode rewards of the last call
+  std::vector<double> spec_chain[2];  // the epsilons of the chain a slot holds (one: {eps})
+  DevBuf<float> chain_rew;            // p2pmg_run_episodes: [n][S] episode rewards of the last call (capacity in floats)
+  int chain_n = 0;
   // pinned host staging of the small per-episode read-backs (episode rewards, metrics): a pageable
   // destination takes HIP's staged copy path (~26 us for 16 KB with the device idle)
-  void* h_small = nullptr;
-  size_t h_small_bytes = 0;
-  int chain_rew_cap = 0, chain_n = 0;
+  PinBuf<char> h_small;
   long long spec_version[2] = {-1, -1};
   long long inputs_version = 0;  // bumped by every input upload (env, profiles, max_in, hp levels)
   long long spec_hits = 0, spec_misses = 0;  // fast-path launches whose pre-pass was / was not ready
-  bool mi_ok = false;         // every max_in inside the fast division range (fdiv in p2pmg_kernels.hip)
-  void* dummy = nullptr;      // fast path: target of masked-off stores (2 * 64 * 32 B)
-  void* rec_pack = nullptr;   // fast path: packed records [T][A] x 32 B
-  int rec_fast_mask = 0;      // records of the last episode that live (packed) in rec_pack
-  int rec_narrow = 0;         // ... as [T][A] float2 {reward, cost} (fast / sq16 with only those two requested)
+  DevBuf<char> dummy;        // fast path: target of masked-off stores (2 * 64 * 32 B)
+  DevBuf<char> rec_pack;     // fast path: packed records [T][A] x 32 B
   int code_src = 0;          // what the code buffer holds: 0 none, 1 replay upload, 2 Philox pre-pass
-  float* ep_reward = nullptr;
-  float* rec_f32[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // reward, cost, grid, p2p, tin
-  uint8_t* rec_action = nullptr;
-  int32_t* rec_index = nullptr;
-  void* rec_stage = nullptr;  // fast / sq16 launches: one staging buffer the packed rows unpack into
-  size_t rec_stage_bytes = 0;
-  double* sum_agent = nullptr;  // p2pmg_episode_summary: [A][16] and [S][16], allocated on first use
-  double* sum_scen = nullptr;
-  float4* hp_lv = nullptr;     // [A] per-agent heat-pump levels
-  float4* thermal = nullptr;   // [A] per-agent {setpoint, lower bound, upper bound, COP} (p2pmg_set_thermal)
-  bool thermal_set = false;    // p2pmg_set_thermal uploaded values (false: the config's, where sq16 applies)
-  float* hp_on = nullptr;      // [A] RuleAgent heat-pump state (lazily allocated, starts off)
-  double* soc = nullptr;       // [A]
-  double* bat_cap = nullptr;   // [A]
-  bool battery = false;
+  DevBuf<float> ep_reward;
+  DevBuf<float> rec_f32[5];  // reward, cost, grid, p2p, tin
+  DevBuf<uint8_t> rec_action;
+  DevBuf<int32_t> rec_index;
+  DevBuf<char> rec_stage;    // fast / sq16 launches: one staging buffer the packed rows unpack into
+  DevBuf<double> sum_agent, sum_scen;  // p2pmg_episode_summary: [A][16] and [S][16], allocated on first use
+  DevBuf<float4> hp_lv;      // [A] per-agent heat-pump levels
+  DevBuf<float4> thermal;    // [A] per-agent {setpoint, lower bound, upper bound, COP} (p2pmg_set_thermal)
+  DevBuf<float> hp_on;       // [A] RuleAgent heat-pump state (lazily allocated, starts off)
+  DevBuf<double> soc, bat_cap;  // [A]
   // operand domains of the battery rule's range-test-free variant (battery_rule_r<false>):
   bool bat_domain = false;   // capacities, SoC bounds, sqrt(eff) and SoC0 in range (set_battery)
   bool prof_bounded = false; // every |load|, |pv| <= 2^100 and finite (set_profiles)
   bool hp_bounded = true;    // every heat-pump level |x| <= 2^100 and finite (defaults: 0 .. 3 kW)
   double bat_min = 0.1, bat_max = 0.9, bat_sqrt_eff = 1.0;
   size_t n_tables = 0;         // Q-tables held: A (shared_q = 0), 1 (1), N (P2PMG_SHARED_ROLE); 0 with the DQN learner
-  bool roles = false;          // cfg.shared_q == P2PMG_SHARED_ROLE
-  long long* qdelta = nullptr; // shared table deltas [kDeltaCopies][n_tables][n_states][4]
+  DevBuf<long long> qdelta;    // shared table deltas [kDeltaCopies][n_tables][n_states][4]
   size_t delta_n() const { return n_tables * n_states * kQPad; }  // entries of one delta replica
   void* comm = nullptr;        // ncclComm_t
   int rank = 0, nranks = 1;    // this context's rank and the world (RCCL communicator or DQN host exchange)
   p2pmg_exchange_fn xfn = nullptr;  // DQN shared network: host gather of the gradient segments
   void* xuser = nullptr;
-  double* d_metrics = nullptr;           // [2] episode-metric sum and count (p2pmg_allreduce_metrics)
-  unsigned long long* d_hash = nullptr;  // [nranks] table fingerprints (p2pmg_table_hash_allgather)
+  DevBuf<double> d_metrics;            // [2] episode-metric sum and count (p2pmg_allreduce_metrics)
+  DevBuf<unsigned long long> d_hash;   // [nranks] table fingerprints (p2pmg_table_hash_allgather)
   bool have_env = false, have_prof = false, have_params = false, have_codes = false;
   // DQN learner (config.learner = P2PMG_LEARNER_DQN)
   bool dqn = false;
   p2pmg_dqn_config dcfg{};
   int n_nets = 0;
-  float* d_theta = nullptr;   // [n_nets][kNetStride]
-  float* d_target = nullptr;
-  float* d_m = nullptr;
-  float* d_v = nullptr;
-  float* d_grad = nullptr;    // shared network: [d_blocks][kNetStride] partials
-  float* d_alt = nullptr;     // shared network: the other half of the Adam double buffer, [4][kNetStride]
-                              // (online, target, m, v) for the act kernel's fused post-exchange Adam step
-  float* d_segs = nullptr;    // [nranks * d_seg_local][kNetStride] gradient segments, global order
-  size_t d_segs_cap = 0;      // floats at d_segs
-  float* h_segs = nullptr;    // pinned host copy of d_segs (host exchange)
-  size_t h_segs_cap = 0;
-  float* d_smp = nullptr;     // [A][32] int32 ring slots sampled for the current step
+  DevBuf<float> d_theta, d_target, d_m, d_v;  // [n_nets][kNetStride]
+  DevBuf<float> d_grad;   // shared network: [d_blocks][kNetStride] partials
+  DevBuf<float> d_alt;    // shared network: the other half of the Adam double buffer, [4][kNetStride]
+                          // (online, target, m, v) for the act kernel's fused post-exchange Adam step
+  DevBuf<float> d_segs;   // [nranks * d_seg_local][kNetStride] gradient segments, global order
+  PinBuf<float> h_segs;   // pinned host copy of d_segs (host exchange)
+  DevBuf<float> d_smp;    // [A][32] int32 ring slots sampled for the current step
   int d_blocks = 0, d_apb = 1;
   int d_seg_local = 1, d_seg_agents = 0, d_bps = 0;  // gradient segments of this context (p2pmg_dqn_config)
-  float* d_buf = nullptr;     // [A][capacity][10]
-  int32_t* d_added = nullptr; // [A]
-  uint16_t* d_samples = nullptr;  // [T][A][32]
-  uint16_t* d_samples_px = nullptr;  // [T][A][32]: a Philox training episode's draws (dqn_sample_prepass_kernel)
+  DevBuf<float> d_buf;       // [A][capacity][10]
+  DevBuf<int32_t> d_added;   // [A]
+  DevBuf<uint16_t> d_samples;     // [T][A][32]
+  DevBuf<uint16_t> d_samples_px;  // [T][A][32]: a Philox training episode's draws (dqn_sample_prepass_kernel)
   bool have_samples = false;
-  float* d_ep_acc = nullptr;  // [S]
-  float* rec_loss = nullptr;  // [T][A]
+  DevBuf<float> d_ep_acc;  // [S]
+  DevBuf<float> rec_loss;  // [T][A]
   std::vector<int64_t> d_steps;  // Adam iterations done, per network (agent.py:310: one optimizer per agent)
-  float* d_lr = nullptr;      // [T][n_nets] per-network step sizes of one episode when the counts differ
-  size_t d_lr_cap = 0;        // floats allocated at d_lr
+  DevBuf<float> d_lr;      // [T][n_nets] per-network step sizes of one episode when the counts differ
   std::vector<float> h_lr;
-  int rec_last_mask = 0;      // records the last episode launch wrote (p2pmg_get_record checks it)
   int64_t d_added_min = 0;    // every ring holds at least this many transitions
   std::string err;
-  std::string last_kernel;
 };
 
 // ---- RCCL, resolved at run time (torch may already have loaded its own librccl; dlopen by
@@ -199,16 +255,11 @@ int fail(p2pmg_ctx* c, int code, const std::string& msg) {
                   std::string(#expr) + ": " + hipGetErrorString(_e));                            \
   } while (0)
 
-template <typename T>
-hipError_t dmalloc(T** p, size_t n) {
-  return hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T) > 0 ? n * sizeof(T) : 16);
-}
-
-template <typename T>
-void dfree(T*& p) {
-  if (p) (void)hipFree(reinterpret_cast<void*>(p));
-  p = nullptr;
-}
+#define RC_TRY(expr)                      \
+  do {                                    \
+    const int _rc = (expr);               \
+    if (_rc != P2PMG_OK) return _rc;      \
+  } while (0)
 
 int rec_slot(int which) {
   switch (which) {
@@ -225,12 +276,53 @@ int rec_slot(int which) {
 int ensure_records(p2pmg_ctx* c, int mask) {
   const size_t ta = (size_t)c->T * c->A;
   for (int b = 0; b < 5; ++b)
-    if ((mask & (1 << b)) && !c->rec_f32[b]) HIP_TRY(c, dmalloc(&c->rec_f32[b], ta));
+    if ((mask & (1 << b)) && !c->rec_f32[b]) HIP_TRY(c, c->rec_f32[b].alloc(ta));
   const size_t tra = (size_t)c->T * (c->R + 1) * c->A;
-  if ((mask & P2PMG_REC_ACTION) && !c->rec_action) HIP_TRY(c, dmalloc(&c->rec_action, tra));
-  if ((mask & P2PMG_REC_INDEX) && !c->rec_index) HIP_TRY(c, dmalloc(&c->rec_index, tra));
-  if ((mask & P2PMG_REC_LOSS) && !c->rec_loss) HIP_TRY(c, dmalloc(&c->rec_loss, ta));
+  if ((mask & P2PMG_REC_ACTION) && !c->rec_action) HIP_TRY(c, c->rec_action.alloc(tra));
+  if ((mask & P2PMG_REC_INDEX) && !c->rec_index) HIP_TRY(c, c->rec_index.alloc(tra));
+  if ((mask & P2PMG_REC_LOSS) && !c->rec_loss) HIP_TRY(c, c->rec_loss.alloc(ta));
   return P2PMG_OK;
+}
+
+// the environment overrides, read once per process on first use
+const p2pmg::Overrides& overrides() {
+  static const p2pmg::Overrides ov = [] {
+    const char *k = getenv("P2PMG_KERNEL"), *w = getenv("P2PMG_SPW"), *n = getenv("P2PMG_NO_SPEC");
+    return p2pmg::Overrides{k && !strcmp(k, "general"), w ? atoi(w) : 0, n && atoi(n) != 0};
+  }();
+  return ov;
+}
+
+// The ring pair a launch is timed with; null events: this launch carries none (timing period).
+struct Timed {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+
+// sampled: only every timing_period-th launch carries events (dispatch-stamped events cost ~4 us per
+// launch at configs[1], ~5 % of an episode).  record: stamp the start here (launches that do not
+// stamp their own events).
+int begin_timed(p2pmg_ctx* c, bool sampled, bool record, Timed* t) {
+  HIP_TRY(c, c->ring.ensure(p2pmg_ctx::kRing));
+  if (sampled && (c->n_launch++ % c->timing_period) != 0) return P2PMG_OK;
+  t->e0 = c->ring.pair(c->n_timed)[0];
+  t->e1 = c->ring.pair(c->n_timed)[1];
+  if (record) HIP_TRY(c, hipEventRecord(t->e0, c->stream));
+  return P2PMG_OK;
+}
+
+int end_timed(p2pmg_ctx* c, const Timed& t, bool record) {
+  if (record && t.e1) HIP_TRY(c, hipEventRecord(t.e1, c->stream));
+  return P2PMG_OK;
+}
+
+// what an episode launch left behind: the one writer of c->last
+void finish_launch(p2pmg_ctx* c, const Timed& t, std::string kernel, int mask, int packed_mask, int narrow) {
+  c->last.kernel = std::move(kernel);
+  c->last.mask = mask;
+  c->last.packed_mask = packed_mask;
+  c->last.narrow = narrow;
+  c->last.timed = true;
+  if (t.e1) c->n_timed++;
 }
 
 }  // namespace
@@ -322,31 +414,29 @@ int p2pmg_create(const p2pmg_config* cfg, int device, p2pmg_ctx** out) {
   if (e != hipSuccess) return bail(P2PMG_E_HIP);
   hipDeviceProp_t prop{};
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(P2PMG_E_HIP);
-  if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) return bail(P2PMG_E_HIP);
+  if (hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking) != hipSuccess) return bail(P2PMG_E_HIP);
   const size_t A = (size_t)c->A;
-  if (dmalloc(&c->prof, (size_t)c->T * A) != hipSuccess || dmalloc(&c->max_in, A) != hipSuccess ||
-      dmalloc(&c->t_in, A) != hipSuccess || dmalloc(&c->t_m, A) != hipSuccess ||
-      dmalloc(&c->ep_reward, (size_t)c->S) != hipSuccess)
+  if (c->prof.alloc((size_t)c->T * A) != hipSuccess || c->max_in.alloc(A) != hipSuccess ||
+      c->t_in.alloc(A) != hipSuccess || c->t_m.alloc(A) != hipSuccess || c->ep_reward.alloc((size_t)c->S) != hipSuccess)
     return bail(P2PMG_E_NOMEM);
   // the code-word buffer always exists: greedy episodes read (and ignore) it, which keeps the
   // kernel's code loads unconditional
   const size_t ncw = (size_t)c->T * ((c->R + 4) / 4) * A;
-  if (dmalloc(&c->codes, ncw) != hipSuccess) return bail(P2PMG_E_NOMEM);
-  if (hipMalloc(&c->dummy, 2 * 64 * p2pmg::kFastRecBytes) != hipSuccess) return bail(P2PMG_E_NOMEM);
+  if (c->codes.alloc(ncw) != hipSuccess) return bail(P2PMG_E_NOMEM);
+  if (c->dummy.alloc(2 * 64 * p2pmg::kFastRecBytes) != hipSuccess) return bail(P2PMG_E_NOMEM);
   if (hipMemsetAsync(c->codes, 0xFF, ncw * 4, c->stream) != hipSuccess) return bail(P2PMG_E_HIP);
   if (cfg->learner != P2PMG_LEARNER_TABULAR && cfg->learner != P2PMG_LEARNER_DQN) return bail(P2PMG_E_INVALID);
   c->dqn = cfg->learner == P2PMG_LEARNER_DQN;
   c->roles = cfg->shared_q == P2PMG_SHARED_ROLE;
   c->n_tables = c->dqn ? 0 : (c->roles ? (size_t)N : cfg->shared_q ? 1 : A);
   const size_t qbytes = c->n_tables * c->n_states * kQPad * c->q_elem;
-  if (hipMalloc(&c->q, qbytes ? qbytes : 16) != hipSuccess) return bail(P2PMG_E_NOMEM);
+  if (c->q.alloc(qbytes) != hipSuccess) return bail(P2PMG_E_NOMEM);
   if (cfg->shared_q && !c->dqn) {
-    if (dmalloc(&c->qdelta, p2pmg::kDeltaCopies * c->delta_n()) != hipSuccess) return bail(P2PMG_E_NOMEM);
+    if (c->qdelta.alloc(p2pmg::kDeltaCopies * c->delta_n()) != hipSuccess) return bail(P2PMG_E_NOMEM);
     if (hipMemsetAsync(c->qdelta, 0, p2pmg::kDeltaCopies * c->delta_n() * 8, c->stream) != hipSuccess)
       return bail(P2PMG_E_HIP);
   }
-  if (dmalloc(&c->hp_lv, A) != hipSuccess || dmalloc(&c->soc, A) != hipSuccess || dmalloc(&c->thermal, A) != hipSuccess)
+  if (c->hp_lv.alloc(A) != hipSuccess || c->soc.alloc(A) != hipSuccess || c->thermal.alloc(A) != hipSuccess)
     return bail(P2PMG_E_NOMEM);
   {
     std::vector<float4> lv(A, make_float4(cfg->hp_levels[0], cfg->hp_levels[1], cfg->hp_levels[2], 0.0f));
@@ -373,64 +463,7 @@ int p2pmg_create(const p2pmg_config* cfg, int device, p2pmg_ctx** out) {
 int p2pmg_destroy(p2pmg_ctx* c) {
   if (!c) return P2PMG_OK;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  dfree(c->env);
-  dfree(c->prof);
-  dfree(c->sqp);
-  dfree(c->max_in);
-  dfree(c->t_in);
-  dfree(c->t_m);
-  if (c->q) (void)hipFree(c->q);
-  dfree(c->codes);
-  for (int k = 0; k < 2; ++k) {
-    dfree(c->pre[k]);
-    dfree(c->pre_ipc[k]);
-    dfree(c->pcodes[k]);
-    c->pcodes_cap[k] = 0;
-  }
-  if (c->dummy) (void)hipFree(c->dummy);
-  if (c->rec_pack) (void)hipFree(c->rec_pack);
-  dfree(c->ep_reward);
-  dfree(c->chain_rew);
-  dfree(c->d_metrics);
-  dfree(c->d_hash);
-  for (auto& b : c->rec_f32) dfree(b);
-  dfree(c->rec_action);
-  dfree(c->rec_index);
-  if (c->rec_stage) (void)hipFree(c->rec_stage);
-  dfree(c->sum_agent);
-  dfree(c->sum_scen);
-  dfree(c->hp_lv);
-  dfree(c->thermal);
-  dfree(c->hp_on);
-  dfree(c->soc);
-  dfree(c->bat_cap);
-  dfree(c->qdelta);
-  dfree(c->d_theta);
-  dfree(c->d_target);
-  dfree(c->d_m);
-  dfree(c->d_v);
-  dfree(c->d_alt);
-  dfree(c->d_lr);
-  dfree(c->d_grad);
-  dfree(c->d_segs);
-  if (c->h_segs) (void)hipHostFree(c->h_segs);
-  if (c->h_small) (void)hipHostFree(c->h_small);
-  dfree(c->d_smp);
-  dfree(c->d_buf);
-  dfree(c->d_added);
-  dfree(c->d_samples);
-  dfree(c->d_samples_px);
-  dfree(c->d_ep_acc);
-  dfree(c->rec_loss);
   if (c->comm && rccl()) rccl()->commDestroy(c->comm);
-  c->comm = nullptr;
-  for (auto& ev : c->ring)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& ev : c->cring)
-    if (ev) (void)hipEventDestroy(ev);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return P2PMG_OK;
 }
@@ -475,8 +508,7 @@ int p2pmg_set_env(p2pmg_ctx* c, int n_env, const float* time, const float* t_out
       r[4] = p2p[k];
     }
   if (c->n_env != n_env) {
-    dfree(c->env);
-    HIP_TRY(c, dmalloc(&c->env, h.size()));
+    HIP_TRY(c, c->env.alloc(h.size()));
     c->n_env = n_env;
   }
   HIP_TRY(c, hipMemcpyAsync(c->env, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -489,13 +521,10 @@ int p2pmg_set_profiles(p2pmg_ctx* c, const float* load_w, const float* pv_w) {
   if (c) c->inputs_version++;  // invalidates the speculative pre-pass slots
   if (!c || !load_w || !pv_w) return P2PMG_E_INVALID;
   const size_t n = (size_t)c->A * c->T;
-  float *dl = nullptr, *dp = nullptr;
-  HIP_TRY(c, dmalloc(&dl, n));
-  hipError_t e = dmalloc(&dp, n);
-  if (e != hipSuccess) {
-    dfree(dl);
-    return fail(c, P2PMG_E_NOMEM, "profile staging");
-  }
+  DevBuf<float> dl, dp;
+  HIP_TRY(c, dl.alloc(n));
+  hipError_t e = dp.alloc(n);
+  if (e != hipSuccess) return fail(c, P2PMG_E_NOMEM, "profile staging");
   {  // the battery rule's range-test-free variant needs bounded, finite balances (p2pmg_kernels.hip)
     bool ok = true;
     for (size_t k = 0; k < n; ++k) ok = ok && std::fabs(load_w[k]) <= 0x1p100f && std::fabs(pv_w[k]) <= 0x1p100f;
@@ -505,8 +534,6 @@ int p2pmg_set_profiles(p2pmg_ctx* c, const float* load_w, const float* pv_w) {
   if (e == hipSuccess) e = hipMemcpyAsync(dp, pv_w, n * 4, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = p2pmg::launch_prof_pack(c->A, c->T, dl, dp, c->prof, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(dl);
-  dfree(dp);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("set_profiles: ") + hipGetErrorString(e));
   c->have_prof = true;
   return P2PMG_OK;
@@ -551,21 +578,19 @@ int p2pmg_reset_temperatures_philox(p2pmg_ctx* c, int episode, double sigma) {
 }
 
 static int ensure_codes(p2pmg_ctx* c) {
-  if (!c->codes) HIP_TRY(c, dmalloc(&c->codes, (size_t)c->T * ((c->R + 4) / 4) * c->A));
+  if (!c->codes) HIP_TRY(c, c->codes.alloc((size_t)c->T * ((c->R + 4) / 4) * c->A));
   return P2PMG_OK;
 }
 
 int p2pmg_set_replay_codes(p2pmg_ctx* c, const uint8_t* codes) {
   if (!c || !codes) return P2PMG_E_INVALID;
   const size_t n = (size_t)c->T * (c->R + 1) * c->A;
-  int rc = ensure_codes(c);
-  if (rc != P2PMG_OK) return rc;
-  uint8_t* staging = nullptr;
-  HIP_TRY(c, dmalloc(&staging, n));
+  RC_TRY(ensure_codes(c));
+  DevBuf<uint8_t> staging;
+  HIP_TRY(c, staging.alloc(n));
   hipError_t e = hipMemcpyAsync(staging, codes, n, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = p2pmg::launch_pack_codes(c->T, c->R + 1, c->A, staging, c->codes, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(staging);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("set_replay_codes: ") + hipGetErrorString(e));
   c->have_codes = true;
   c->code_src = 1;
@@ -591,14 +616,13 @@ int p2pmg_set_q(p2pmg_ctx* c, int first, int count, const void* host, int host_d
   if (!q_range_ok(c, first, count, host, host_dtype)) return fail(c, P2PMG_E_INVALID, "set_q: bad range/dtype");
   const int na = c->cfg.n_actions;
   const size_t hbytes = (size_t)count * c->n_states * na * (host_dtype == P2PMG_Q_F64 ? 8 : 4);
-  void* staging = nullptr;
-  HIP_TRY(c, hipMalloc(&staging, hbytes ? hbytes : 16));
+  DevBuf<char> staging;
+  HIP_TRY(c, staging.alloc(hbytes));
   char* dst = static_cast<char*>(c->q) + (size_t)first * c->n_states * kQPad * c->q_elem;
   hipError_t e = hipMemcpyAsync(staging, host, hbytes, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess)
     e = p2pmg::launch_q_pack(count, c->n_states, na, staging, dst, c->cfg.q_dtype, host_dtype, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(staging);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("set_q: ") + hipGetErrorString(e));
   return P2PMG_OK;
 }
@@ -607,15 +631,25 @@ int p2pmg_get_q(p2pmg_ctx* c, int first, int count, void* host, int host_dtype) 
   if (!q_range_ok(c, first, count, host, host_dtype)) return fail(c, P2PMG_E_INVALID, "get_q: bad range/dtype");
   const int na = c->cfg.n_actions;
   const size_t hbytes = (size_t)count * c->n_states * na * (host_dtype == P2PMG_Q_F64 ? 8 : 4);
-  void* staging = nullptr;
-  HIP_TRY(c, hipMalloc(&staging, hbytes ? hbytes : 16));
+  DevBuf<char> staging;
+  HIP_TRY(c, staging.alloc(hbytes));
   const char* src = static_cast<const char*>(c->q) + (size_t)first * c->n_states * kQPad * c->q_elem;
   hipError_t e = p2pmg::launch_q_unpack(count, c->n_states, na, src, staging, c->cfg.q_dtype, host_dtype, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(host, staging, hbytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(staging);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("get_q: ") + hipGetErrorString(e));
   return P2PMG_OK;
+}
+
+// the unpacked record arrays as they exist now (ensure_records allocates them on demand)
+static void bind_records(p2pmg_ctx* c, EpisodeParams& p) {
+  p.rec_reward = c->rec_f32[0];
+  p.rec_cost = c->rec_f32[1];
+  p.rec_grid = c->rec_f32[2];
+  p.rec_p2p = c->rec_f32[3];
+  p.rec_tin = c->rec_f32[4];
+  p.rec_action = c->rec_action;
+  p.rec_index = c->rec_index;
 }
 
 static EpisodeParams episode_params(p2pmg_ctx* c, const p2pmg_episode_args* args) {
@@ -645,13 +679,7 @@ static EpisodeParams episode_params(p2pmg_ctx* c, const p2pmg_episode_args* args
   p.seed_lo = (uint32_t)(g.seed & 0xFFFFFFFFu);
   p.seed_hi = (uint32_t)(g.seed >> 32);
   p.agent_offset = (uint32_t)(g.scenario_offset * c->N);
-  p.rec_reward = c->rec_f32[0];
-  p.rec_cost = c->rec_f32[1];
-  p.rec_grid = c->rec_f32[2];
-  p.rec_p2p = c->rec_f32[3];
-  p.rec_tin = c->rec_f32[4];
-  p.rec_action = c->rec_action;
-  p.rec_index = c->rec_index;
+  bind_records(c, p);
   p.ep_reward = c->ep_reward;
   p.shared_q = c->roles ? 2 : g.shared_q ? 1 : 0;
   p.qdelta = c->qdelta;
@@ -695,27 +723,6 @@ static EpisodeParams episode_params(p2pmg_ctx* c, const p2pmg_episode_args* args
 
 static int dqn_run_episode(p2pmg_ctx* c, const p2pmg_episode_args* args);
 
-// divisors the fast kernel divides by with the range-free quotient (fdiv_b in p2pmg_kernels.hip)
-static bool host_div_range(float b) {
-  const float m = std::fabs(b);
-  return m >= 0x1p-40f && m <= 0x1p40f;
-}
-
-// fast per-agent-table path (episode_fast_kernel): automatic whenever it applies
-static bool fast_applies(const p2pmg_ctx* c, const p2pmg_episode_args* args) {
-  static const bool env_general = [] { const char* v = getenv("P2PMG_KERNEL"); return v && !strcmp(v, "general"); }();
-  const p2pmg_config& g = c->cfg;
-  return !g.shared_q && (!c->battery || c->R + 1 <= p2pmg::kFastBatMaxR1) && c->N <= 8 && c->R + 1 <= 4 && c->mi_ok &&
-         (long long)g.n_time_states * g.n_temp_states * g.n_balance_states < 65536 &&
-         // a wave's 64 tables span < 4 GiB (the gathers' 32-bit offsets)
-         64LL * g.n_time_states * g.n_temp_states * g.n_balance_states * g.n_p2p_states * 4 * (g.q_dtype == 0 ? 8 : 4) <
-             (1LL << 32) &&
-         (long long)c->T * c->A < (1LL << 32) && host_div_range(g.minutes_per_hour) &&
-         g.temp_margin == 1.0f &&  // heating.py:90 (the kernel skips the / margin)
-         !(args->flags & (P2PMG_FLAG_GENERAL_KERNEL | P2PMG_FLAG_TILE_KERNEL | P2PMG_FLAG_PHILOX_INKERNEL)) &&
-         !env_general;
-}
-
 // a chained fast-path launch (p2pmg_run_episodes): n episodes at eps[0..n), the caller's guess of
 // the next chain (next_n episodes at next_eps) for the speculative pre-pass, rewards [n][S] on device
 struct ChainReq {
@@ -734,6 +741,110 @@ int p2pmg_run_episode(p2pmg_ctx* c, const p2pmg_episode_args* args) {
   return run_episode_impl(c, args, nullptr);
 }
 
+// fast / sq16 write packed rows (rec_pack) that p2pmg_get_record unpacks into one staging buffer, so
+// those launches allocate no [T][A] arrays per record (configs[3] at full size: 35 GB less)
+static int ensure_rec_pack(p2pmg_ctx* c, const p2pmg_episode_args* args) {
+  if (args->record && !c->rec_pack) HIP_TRY(c, c->rec_pack.alloc((size_t)c->T * c->A * p2pmg::kFastRecBytes));
+  return P2PMG_OK;
+}
+
+// The fast kernel: both pre-pass slots and their code words, this slot's pre-pass unless the previous
+// launch computed it, and the next slot's description (next) for this launch's producer workgroups.
+static int prepare_fast(p2pmg_ctx* c, const p2pmg_episode_args* args, const ChainReq* ch, const EpisodePlan& plan,
+                        EpisodeParams& p, p2pmg::PrepOut* next) {
+  const int ps = c->pslot;
+  const size_t ta = (size_t)c->T * c->A;
+  const size_t wpe = ta * ((c->R + 4) / 4);  // code words per episode
+  const bool philox = plan.philox == p2pmg::Philox::FastPrepass;
+  // this launch's chain (one episode unless chained) and the caller's guess of the next launch's:
+  // P2PMG_FLAG_NEXT_EPSILON: next_epsilon is the guess as given (0 included); without it a
+  // positive next_epsilon is the guess and anything else means "the same epsilon"
+  std::vector<double> cur(ch ? ch->eps : &args->epsilon, ch ? ch->eps + ch->n : &args->epsilon + 1);
+  std::vector<double> nxt_eps;
+  if (ch) {
+    if (ch->next_n > 0) nxt_eps.assign(ch->next_eps, ch->next_eps + ch->next_n);
+    else nxt_eps.assign(cur.size(), cur.back());
+  } else {
+    const bool have_next = (args->flags & P2PMG_FLAG_NEXT_EPSILON) != 0 || args->next_epsilon > 0.0;
+    nxt_eps.assign(1, have_next ? args->next_epsilon : args->epsilon);
+  }
+  const int n_ep = (int)cur.size(), n_next = (int)nxt_eps.size();
+  for (int k = 0; k < 2; ++k) {  // both slots (the launch writes the other one)
+    if (!c->pre[k]) HIP_TRY(c, c->pre[k].alloc(ta));
+    if (plan.want_ipc && !c->pre_ipc[k]) HIP_TRY(c, c->pre_ipc[k].alloc(ta));
+    const size_t need = wpe * (size_t)std::max(n_ep, n_next);
+    if (philox && c->pcodes[k].cap() < need) {  // chains: their full capacity at once (no reallocation later)
+      c->spec_valid[k] = false;
+      HIP_TRY(c, c->pcodes[k].alloc(std::max(need, wpe * (size_t)(ch ? ch->reserve : 1))));
+    }
+  }
+  p.pre_ipc = plan.want_ipc ? c->pre_ipc[ps].get() : nullptr;
+  if (philox) p.codes = c->pcodes[ps];
+  p.rng = 0;
+  p.chain = n_ep;
+  p.codes_stride = wpe;
+  p.chain_rewards = ch ? ch->rewards : nullptr;
+  RC_TRY(ensure_rec_pack(c, args));
+  auto prep_out = [&](int slot, int episode, const std::vector<double>& eps) {
+    p2pmg::PrepOut o{c->pre[slot], plan.want_ipc ? c->pre_ipc[slot].get() : nullptr,
+                     philox ? c->pcodes[slot].get() : nullptr, episode, eps[0], 0u, 0};
+    p2pmg::eps_threshold(eps[0], o.eps_thr, o.eps_all);
+    o.n_ep = (int)eps.size();
+    o.words_stride = wpe;
+    o.ep_all = 0;
+    for (int k = 0; k < o.n_ep; ++k) {
+      int all = 0;
+      p2pmg::eps_threshold(eps[k], o.ep_thr[k], all);
+      o.ep_all |= (uint64_t)all << k;
+    }
+    return o;
+  };
+  // this slot's pre-pass: computed by the previous launch if it guessed these arguments
+  const bool hit = c->spec_valid[ps] && c->spec_version[ps] == c->inputs_version &&
+                   (!philox || (c->spec_episode[ps] == args->episode && c->spec_chain[ps] == cur));
+  if (!hit) HIP_TRY(c, p2pmg::launch_step_prepass(p, prep_out(ps, args->episode, cur), c->stream));
+  // the next slot, for the episodes after this launch's at the caller's guess (the decay schedule
+  // is known, community.py:279-286).  Philox draws only when this one has them.
+  const int ns = ps ^ 1;
+  *next = prep_out(ns, args->episode + n_ep, nxt_eps);
+  if (hit) c->spec_hits++;
+  else c->spec_misses++;
+  c->spec_valid[ns] = plan.speculate;
+  c->spec_version[ns] = c->inputs_version;
+  c->spec_episode[ns] = philox ? args->episode + n_ep : -1;
+  c->spec_chain[ns] = nxt_eps;
+  return P2PMG_OK;
+}
+
+// The sq16 kernel: the step words {balance, time / balance row offset}, recomputed after any input upload
+static int prepare_sq16(p2pmg_ctx* c, const p2pmg_episode_args* args, EpisodeParams& p) {
+  RC_TRY(ensure_rec_pack(c, args));
+  p.rec_pack = c->rec_pack;
+  if (!c->sqp) HIP_TRY(c, c->sqp.alloc((size_t)c->T * c->A));
+  if (c->sqp_version != c->inputs_version) {
+    HIP_TRY(c, p2pmg::launch_sq16_prep(p, c->sqp, c->stream));
+    c->sqp_version = c->inputs_version;
+  }
+  p.sqp = c->sqp;
+  return P2PMG_OK;
+}
+
+// The general kernel (either form): unpacked record arrays, and the Philox code words where the
+// plan draws them ahead of the launch
+static int prepare_general(p2pmg_ctx* c, const p2pmg_episode_args* args, const EpisodePlan& plan, EpisodeParams& p) {
+  RC_TRY(ensure_records(c, args->record));
+  bind_records(c, p);
+  if (plan.philox != p2pmg::Philox::CodesPrepass) return P2PMG_OK;
+  RC_TRY(ensure_codes(c));
+  p.codes = c->codes;
+  HIP_TRY(c, p2pmg::launch_philox_codes(p, c->codes, c->stream));
+  c->code_src = 2;
+  c->have_codes = false;  // a replay upload must be repeated after a pre-pass overwrote it
+  p.rng = 0;
+  return P2PMG_OK;
+}
+
+// validate -> plan -> prepare the plan's family -> launch -> finish_launch
 static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const ChainReq* ch) {
   if (!c || !args) return P2PMG_E_INVALID;
   if (c->dqn) return dqn_run_episode(c, args);
@@ -744,179 +855,40 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
   if (train && args->rng != P2PMG_RNG_REPLAY && args->rng != P2PMG_RNG_PHILOX) return fail(c, P2PMG_E_INVALID, "rng");
   if (train && args->rng == P2PMG_RNG_REPLAY && !c->have_codes)
     return fail(c, P2PMG_E_STATE, "run_episode: replay mode needs p2pmg_set_replay_codes");
-  int rc = P2PMG_OK;
+  const EpisodePlan plan = p2pmg::plan_episode(*c, *args, ch != nullptr, overrides());
+  if (plan.error) return fail(c, P2PMG_E_INVALID, plan.error);
   const p2pmg_config& g = c->cfg;
-  static const int env_spw = [] { const char* v = getenv("P2PMG_SPW"); return v ? atoi(v) : 0; }();
-  static const bool env_general = [] { const char* v = getenv("P2PMG_KERNEL"); return v && !strcmp(v, "general"); }();
-  const bool fast = fast_applies(c, args);
-  if (ch && !(fast && train && args->rng == P2PMG_RNG_PHILOX))
-    return fail(c, P2PMG_E_INVALID, "run_episode: a chained launch needs the fast kernel and Philox training");
-  // shared table, 16-agent scenarios (configs[2]): episode_sq16_kernel
-  const bool sq16 = g.shared_q && !c->roles && c->N == 16 && c->R <= 1 && c->mi_ok && host_div_range(g.minutes_per_hour) &&
-                    (long long)c->T * c->A < (1LL << 32) && (long long)c->T * c->n_env * p2pmg::kEnvStride < (1LL << 32) &&
-                    host_div_range(g.temp_margin) && g.n_time_states == 20 && g.n_temp_states == 20 &&
-                    g.n_balance_states == 20 && g.n_p2p_states == 20 &&
-                    !c->thermal_set &&  // per-agent thermal parameters: the general kernel's shared-table form
-                    !(args->flags & (P2PMG_FLAG_GENERAL_KERNEL | P2PMG_FLAG_TILE_KERNEL)) && !env_general;
-  // the general kernel writes unpacked records; fast / sq16 write packed rows (rec_pack) that
-  // p2pmg_get_record unpacks into one staging buffer, so those launches allocate no [T][A] arrays
-  // per record (configs[3] at full size: 35 GB less)
-  if (!fast && !sq16) {
-    rc = ensure_records(c, args->record);
-    if (rc != P2PMG_OK) return rc;
-  }
+  const bool fast = plan.family == Family::Fast, sq16 = plan.family == Family::Sq16, tile = plan.family == Family::Tile;
+  const bool ext = plan.packed_records;
   EpisodeParams p = episode_params(c, args);
   const int ps = c->pslot;
   p2pmg::PrepOut next{};
-  bool produce = false;
-  if (fast) {
-    const size_t ta = (size_t)c->T * c->A;
-    const size_t wpe = ta * ((c->R + 4) / 4);  // code words per episode
-    const bool philox = train && args->rng == P2PMG_RNG_PHILOX;
-    const bool want_ipc = c->N == 2 && c->R >= 1 && !c->battery;  // the kernel's CAND path
-    // this launch's chain (one episode unless chained) and the caller's guess of the next launch's:
-    // P2PMG_FLAG_NEXT_EPSILON: next_epsilon is the guess as given (0 included); without it a
-    // positive next_epsilon is the guess and anything else means "the same epsilon"
-    std::vector<double> cur(ch ? ch->eps : &args->epsilon, ch ? ch->eps + ch->n : &args->epsilon + 1);
-    std::vector<double> nxt_eps;
-    if (ch) {
-      if (ch->next_n > 0) nxt_eps.assign(ch->next_eps, ch->next_eps + ch->next_n);
-      else nxt_eps.assign(cur.size(), cur.back());
-    } else {
-      const bool have_next = (args->flags & P2PMG_FLAG_NEXT_EPSILON) != 0 || args->next_epsilon > 0.0;
-      nxt_eps.assign(1, have_next ? args->next_epsilon : args->epsilon);
-    }
-    const int n_ep = (int)cur.size(), n_next = (int)nxt_eps.size();
-    for (int k = 0; k < 2; ++k) {  // both slots (the launch writes the other one)
-      if (!c->pre[k]) HIP_TRY(c, dmalloc(&c->pre[k], ta));
-      if (want_ipc && !c->pre_ipc[k]) HIP_TRY(c, dmalloc(&c->pre_ipc[k], ta));
-      const size_t need = wpe * (size_t)std::max(n_ep, n_next);
-      if (philox && c->pcodes_cap[k] < need) {  // chains: their full capacity at once (no reallocation later)
-        const size_t cap = std::max(need, wpe * (size_t)(ch ? ch->reserve : 1));
-        dfree(c->pcodes[k]);
-        c->pcodes_cap[k] = 0;
-        c->spec_valid[k] = false;
-        HIP_TRY(c, dmalloc(&c->pcodes[k], cap));
-        c->pcodes_cap[k] = cap;
-      }
-    }
-    p.pre_ipc = want_ipc ? c->pre_ipc[ps] : nullptr;
-    if (philox) p.codes = c->pcodes[ps];
-    p.rng = 0;
-    p.chain = n_ep;
-    p.codes_stride = wpe;
-    p.chain_rewards = ch ? ch->rewards : nullptr;
-    if (args->record && !c->rec_pack) HIP_TRY(c, hipMalloc(&c->rec_pack, ta * p2pmg::kFastRecBytes));
-    auto prep_out = [&](int slot, int episode, const std::vector<double>& eps) {
-      p2pmg::PrepOut o{c->pre[slot], want_ipc ? c->pre_ipc[slot] : nullptr, philox ? c->pcodes[slot] : nullptr,
-                       episode, eps[0], 0u, 0};
-      p2pmg::eps_threshold(eps[0], o.eps_thr, o.eps_all);
-      o.n_ep = (int)eps.size();
-      o.words_stride = wpe;
-      o.ep_all = 0;
-      for (int k = 0; k < o.n_ep; ++k) {
-        int all = 0;
-        p2pmg::eps_threshold(eps[k], o.ep_thr[k], all);
-        o.ep_all |= (uint64_t)all << k;
-      }
-      return o;
-    };
-    // this slot's pre-pass: computed by the previous launch if it guessed these arguments
-    const bool hit = c->spec_valid[ps] && c->spec_version[ps] == c->inputs_version &&
-                     (!philox || (c->spec_episode[ps] == args->episode && c->spec_chain[ps] == cur));
-    if (!hit) HIP_TRY(c, p2pmg::launch_step_prepass(p, prep_out(ps, args->episode, cur), c->stream));
-    // the next slot, for the episodes after this launch's at the caller's guess (the decay schedule
-    // is known, community.py:279-286).  Philox draws only when this one has them.
-    // P2PMG_NO_SPEC=1 (profiling only): no producer blocks, so the episode kernel's counters are its own
-    static const bool env_no_spec = [] { const char* v = getenv("P2PMG_NO_SPEC"); return v && atoi(v) != 0; }();
-    const int ns = ps ^ 1;
-    next = prep_out(ns, args->episode + n_ep, nxt_eps);
-    produce = !env_no_spec;
-    if (hit) c->spec_hits++;
-    else c->spec_misses++;
-    c->spec_valid[ns] = produce;
-    c->spec_version[ns] = c->inputs_version;
-    c->spec_episode[ns] = philox ? args->episode + n_ep : -1;
-    c->spec_chain[ns] = nxt_eps;
-  } else if (train && args->rng == P2PMG_RNG_PHILOX) {
-    bool prepass = c->A < (1 << 18) && !sq16;  // sq16: throughput-bound, draws in the kernel
-    if (args->flags & P2PMG_FLAG_PHILOX_PREPASS) prepass = true;
-    if (args->flags & P2PMG_FLAG_PHILOX_INKERNEL) prepass = false;
-    if (prepass) {
-      rc = ensure_codes(c);
-      if (rc != P2PMG_OK) return rc;
-      p.codes = c->codes;
-      HIP_TRY(c, p2pmg::launch_philox_codes(p, c->codes, c->stream));
-      c->code_src = 2;
-      c->have_codes = false;  // a replay upload must be repeated after a pre-pass overwrote it
-      p.rng = 0;
-    }
-  }
-  if (c->ring.empty()) {
-    c->ring.assign(2 * p2pmg_ctx::kRing, nullptr);
-    for (auto& ev : c->ring) HIP_TRY(c, hipEventCreate(&ev));
-  }
-  // dispatch-stamped events cost ~4 us per launch at configs[1] (~5 % of an episode): with a
-  // timing period k only every k-th launch carries them
-  const bool stamp = (c->n_launch++ % c->timing_period) == 0;
-  const int slot = (int)(c->n_timed % p2pmg_ctx::kRing);
-  hipEvent_t r0 = stamp ? c->ring[2 * slot] : nullptr, r1 = stamp ? c->ring[2 * slot + 1] : nullptr;
-  if (sq16) {
-    if (args->record && !c->rec_pack)
-      HIP_TRY(c, hipMalloc(&c->rec_pack, (size_t)c->T * c->A * p2pmg::kFastRecBytes));
-    p.rec_pack = c->rec_pack;
-    // the step words {balance, time / balance row offset}: recomputed after any input upload
-    if (!c->sqp) HIP_TRY(c, dmalloc(&c->sqp, (size_t)c->T * c->A));
-    if (c->sqp_version != c->inputs_version) {
-      HIP_TRY(c, p2pmg::launch_sq16_prep(p, c->sqp, c->stream));
-      c->sqp_version = c->inputs_version;
-    }
-    p.sqp = c->sqp;
-  }
-  // fast / sq16: only {reward, cost} requested -> 8-B record rows
-  p.rec_narrow = (fast || sq16) && (args->record & ~(P2PMG_REC_REWARD | P2PMG_REC_COST)) == 0 ? 1 : 0;
-  const bool ext = fast || sq16;  // launches that stamp their own timing events
-  if (!ext && stamp) HIP_TRY(c, hipEventRecord(r0, c->stream));
-  int spw = args->scen_per_wave > 0 ? args->scen_per_wave : env_spw;
-  if (spw <= 0) {  // automatic: full waves, or spread a small batch over all CUs (one wave per CU)
-    const int full = 64 / (c->N <= 1 ? 1 : c->N <= 2 ? 2 : c->N <= 4 ? 4 : 8);
-    const int waves = (c->S + full - 1) / full;
-    spw = waves >= c->n_cu ? full : std::max(full / 4, (c->S + c->n_cu - 1) / c->n_cu);
-    // below epsilon 0.5 most lanes are greedy (a round-0 row gather and two argmaxes on every step):
-    // there half-filled waves, two per CU, measured faster (configs[1], chained: 80.7 -> 77.9 us per
-    // episode at epsilon 0.1, 76.1 -> 75.0 at 0.39, even at 0.53), above it one wave per CU
-    // (71.7 against 73.9 us at 0.729): profiles/r05_chain/spw_epsilon.txt
-    if (fast && train && args->epsilon < 0.5 && waves < c->n_cu) spw = std::max(full / 4, (spw + 1) / 2);
-    spw = std::min(spw, full);
-  }
+  RC_TRY(fast ? prepare_fast(c, args, ch, plan, p, &next) : sq16 ? prepare_sq16(c, args, p) : prepare_general(c, args, plan, p));
+  p.rec_narrow = plan.rec_narrow;
   const bool reset = (args->flags & P2PMG_FLAG_RESET_T0) != 0;
-  // the general kernel's LDS-tile form: every N outside {1..8, 16}, or any N on request
-  const bool tile = !fast && !sq16 &&
-                    ((args->flags & P2PMG_FLAG_TILE_KERNEL) != 0 || !((c->N >= 1 && c->N <= 8) || c->N == 16));
   p.reset_t0 = (ext && reset) ? 1 : 0;
   p.reset_sigma = args->reset_sigma;
-  hipError_t e = fast   ? p2pmg::launch_episode_fast(p, c->pre[ps], c->rec_pack, g.q_dtype, spw,
-                                                    produce ? &next : nullptr, r0, r1, c->stream)
-                 : sq16 ? p2pmg::launch_episode_sq16(p, g.q_dtype, r0, r1, c->stream)
+  Timed tm;
+  RC_TRY(begin_timed(c, true, !ext, &tm));
+  hipError_t e = fast   ? p2pmg::launch_episode_fast(p, c->pre[ps], c->rec_pack, g.q_dtype, plan.spw,
+                                                    plan.speculate ? &next : nullptr, tm.e0, tm.e1, c->stream)
+                 : sq16 ? p2pmg::launch_episode_sq16(p, g.q_dtype, tm.e0, tm.e1, c->stream)
                         : p2pmg::launch_episode(p, g.q_dtype, tile, c->stream);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("episode launch: ") + hipGetErrorString(e));
-  c->rec_fast_mask = ext ? (args->record & 127) : 0;
-  c->rec_last_mask = args->record;
-  c->rec_narrow = (fast || sq16) ? p.rec_narrow : 0;
-  c->last_kernel = std::string(fast ? "episode_fast_kernel<" : sq16 ? "episode_sq16_kernel<" : "episode_kernel<") +
-                   std::to_string(c->N) + (tile ? ",tile" + std::to_string(p2pmg::general_tile_cap(c->N)) : "") + "," +
-                   (g.q_dtype == 0 ? "f64" : "f32") + ",R1=" + std::to_string(c->R + 1) +
-                   (ext ? (train ? ",train" : ",greedy") : "") + (g.shared_q ? ",shared" : "") + (c->roles ? ",roles" : "") +
-                   (c->battery ? (ext && !p.bat_safe ? ",battery,range-checked>" : ",battery>") : ">");
-  if (!ext && stamp) HIP_TRY(c, hipEventRecord(r1, c->stream));
+  RC_TRY(end_timed(c, tm, !ext));
   if (fast) c->pslot ^= 1;
   if (reset && !ext) {  // general kernel: the reset as its own launch
     const uint32_t off = (uint32_t)(g.scenario_offset * c->N);
     HIP_TRY(c, p2pmg::launch_t0_philox(c->A, c->t_in, c->t_m, p.seed_lo, p.seed_hi, args->episode + 1, off,
                                        c->thermal, args->reset_sigma, c->stream));
   }
-  c->timed = true;
-  if (stamp) c->n_timed++;
+  finish_launch(c, tm,
+                std::string(fast ? "episode_fast_kernel<" : sq16 ? "episode_sq16_kernel<" : "episode_kernel<") +
+                    std::to_string(c->N) + (tile ? ",tile" + std::to_string(p2pmg::general_tile_cap(c->N)) : "") + "," +
+                    (g.q_dtype == 0 ? "f64" : "f32") + ",R1=" + std::to_string(c->R + 1) +
+                    (ext ? (train ? ",train" : ",greedy") : "") + (g.shared_q ? ",shared" : "") + (c->roles ? ",roles" : "") +
+                    (c->battery ? (ext && !p.bat_safe ? ",battery,range-checked>" : ",battery>") : ">"),
+                args->record, ext ? (args->record & 127) : 0, plan.rec_narrow);
   return P2PMG_OK;
 }
 
@@ -925,15 +897,10 @@ int p2pmg_run_episodes(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, cons
   if (!c || !args || n < 1 || !epsilons || (next_n > 0 && !next_epsilons)) return P2PMG_E_INVALID;
   if (!c->dqn && (!c->have_env || !c->have_prof || !c->have_params))
     return fail(c, P2PMG_E_STATE, "run_episodes: env, profiles and agent params must be set first");
-  if (c->chain_rew_cap < n) {  // at least one full chain's worth, so a caller's chains never reallocate
-    const int cap = std::max(n, p2pmg::kMaxChain);
-    dfree(c->chain_rew);
-    c->chain_rew_cap = 0;
-    HIP_TRY(c, dmalloc(&c->chain_rew, (size_t)cap * c->S));
-    c->chain_rew_cap = cap;
-  }
+  // at least one full chain's worth, so a caller's chains never reallocate
+  HIP_TRY(c, c->chain_rew.grow((size_t)std::max(n, p2pmg::kMaxChain) * c->S));
   c->chain_n = 0;
-  const bool chain = !c->dqn && args->mode == P2PMG_MODE_TRAIN && args->rng == P2PMG_RNG_PHILOX && fast_applies(c, args);
+  const bool chain = !c->dqn && p2pmg::plan_episode(*c, *args, false, overrides()).philox == p2pmg::Philox::FastPrepass;
   p2pmg_episode_args a = *args;
   if (!chain) {  // one launch per episode, the same results
     for (int k = 0; k < n; ++k) {
@@ -941,8 +908,7 @@ int p2pmg_run_episodes(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, cons
       a.epsilon = epsilons[k];
       a.flags = args->flags | P2PMG_FLAG_NEXT_EPSILON;
       a.next_epsilon = k + 1 < n ? epsilons[k + 1] : next_n > 0 ? next_epsilons[0] : epsilons[k];
-      const int rc = run_episode_impl(c, &a, nullptr);
-      if (rc != P2PMG_OK) return rc;
+      RC_TRY(run_episode_impl(c, &a, nullptr));
       HIP_TRY(c, hipMemcpyAsync(c->chain_rew + (size_t)k * c->S, c->ep_reward,
                                 (size_t)c->S * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
@@ -965,8 +931,7 @@ int p2pmg_run_episodes(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, cons
     }
     a.episode = args->episode + k0;
     a.epsilon = epsilons[k0];
-    const int rc = run_episode_impl(c, &a, &req);
-    if (rc != P2PMG_OK) return rc;
+    RC_TRY(run_episode_impl(c, &a, &req));
   }
   c->chain_n = n;
   return P2PMG_OK;
@@ -989,15 +954,14 @@ int p2pmg_set_timing_period(p2pmg_ctx* c, int period) {
 
 static int ensure_hp_on(p2pmg_ctx* c) {
   if (c->hp_on) return P2PMG_OK;
-  HIP_TRY(c, dmalloc(&c->hp_on, (size_t)c->A));
+  HIP_TRY(c, c->hp_on.alloc((size_t)c->A));
   HIP_TRY(c, hipMemsetAsync(c->hp_on, 0, (size_t)c->A * sizeof(float), c->stream));
   return P2PMG_OK;
 }
 
 int p2pmg_set_hp_state(p2pmg_ctx* c, const float* on) {
   if (!c || !on) return P2PMG_E_INVALID;
-  int rc = ensure_hp_on(c);
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(ensure_hp_on(c));
   HIP_TRY(c, hipMemcpyAsync(c->hp_on, on, (size_t)c->A * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return P2PMG_OK;
@@ -1005,8 +969,7 @@ int p2pmg_set_hp_state(p2pmg_ctx* c, const float* on) {
 
 int p2pmg_get_hp_state(p2pmg_ctx* c, float* on) {
   if (!c || !on) return P2PMG_E_INVALID;
-  int rc = ensure_hp_on(c);
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(ensure_hp_on(c));
   HIP_TRY(c, hipMemcpyAsync(on, c->hp_on, (size_t)c->A * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return P2PMG_OK;
@@ -1028,30 +991,20 @@ int p2pmg_run_rule_episode(p2pmg_ctx* c, int record) {
   args.mode = P2PMG_MODE_GREEDY;
   args.record = rec;
   EpisodeParams p = episode_params(c, &args);
-  if (c->ring.empty()) {
-    c->ring.assign(2 * p2pmg_ctx::kRing, nullptr);
-    for (auto& ev : c->ring) HIP_TRY(c, hipEventCreate(&ev));
-  }
-  const int slot = (int)(c->n_timed % p2pmg_ctx::kRing);
-  HIP_TRY(c, hipEventRecord(c->ring[2 * slot], c->stream));
+  Timed tm;
+  RC_TRY(begin_timed(c, false, true, &tm));
   HIP_TRY(c, p2pmg::launch_rule_episode(p, c->hp_on, c->stream));
-  HIP_TRY(c, hipEventRecord(c->ring[2 * slot + 1], c->stream));
-  c->rec_fast_mask = 0;
-  c->rec_last_mask = rec;
-  c->last_kernel = "rule_episode_kernel<" + std::to_string(c->N) + ">";
-  c->timed = true;
-  c->n_timed++;
+  RC_TRY(end_timed(c, tm, true));
+  finish_launch(c, tm, "rule_episode_kernel<" + std::to_string(c->N) + ">", rec, 0, 0);
   return P2PMG_OK;
 }
 
-const char* p2pmg_last_kernel(const p2pmg_ctx* c) { return c ? c->last_kernel.c_str() : ""; }
+const char* p2pmg_last_kernel(const p2pmg_ctx* c) { return c ? c->last.kernel.c_str() : ""; }
 
 int p2pmg_last_kernel_ms(p2pmg_ctx* c, float* ms) {
   if (!c || !ms) return P2PMG_E_INVALID;
-  if (!c->timed || c->n_timed == 0) return fail(c, P2PMG_E_STATE, "no episode launched yet");
-  const int slot = (int)((c->n_timed - 1) % p2pmg_ctx::kRing);  // the ring pair of the last launch
-  HIP_TRY(c, hipEventSynchronize(c->ring[2 * slot + 1]));
-  HIP_TRY(c, hipEventElapsedTime(ms, c->ring[2 * slot], c->ring[2 * slot + 1]));
+  if (!c->last.timed || c->n_timed == 0) return fail(c, P2PMG_E_STATE, "no episode launched yet");
+  HIP_TRY(c, c->ring.elapsed(c->n_timed - 1, ms));  // the ring pair of the last launch
   return P2PMG_OK;
 }
 
@@ -1060,11 +1013,7 @@ int p2pmg_kernel_times(p2pmg_ctx* c, float* ms, int max, int* count) {
   const long long n = c->n_timed < p2pmg_ctx::kRing ? c->n_timed : p2pmg_ctx::kRing;
   const long long first = c->n_timed - n;
   int w = 0;
-  for (long long k = first; k < c->n_timed && w < max; ++k, ++w) {
-    const int slot = (int)(k % p2pmg_ctx::kRing);
-    HIP_TRY(c, hipEventSynchronize(c->ring[2 * slot + 1]));
-    HIP_TRY(c, hipEventElapsedTime(&ms[w], c->ring[2 * slot], c->ring[2 * slot + 1]));
-  }
+  for (long long k = first; k < c->n_timed && w < max; ++k, ++w) HIP_TRY(c, c->ring.elapsed(k, &ms[w]));
   *count = w;
   return P2PMG_OK;
 }
@@ -1102,19 +1051,13 @@ int p2pmg_get_record(p2pmg_ctx* c, int which, void* host) {
   } else {
     return fail(c, P2PMG_E_INVALID, "get_record: unknown record");
   }
-  if (!(c->rec_last_mask & which))
+  if (!(c->last.mask & which))
     return fail(c, P2PMG_E_STATE, "get_record: the last episode launch did not record this");
-  if (c->rec_fast_mask & which) {  // the last episode ran the fast / sq16 kernel: unpack its rows
-    if (c->rec_stage_bytes < bytes) {
-      if (c->rec_stage) (void)hipFree(c->rec_stage);
-      c->rec_stage = nullptr;
-      c->rec_stage_bytes = 0;
-      HIP_TRY(c, hipMalloc(&c->rec_stage, bytes));
-      c->rec_stage_bytes = bytes;
-    }
+  if (c->last.packed_mask & which) {  // the last episode ran the fast / sq16 kernel: unpack its rows
+    HIP_TRY(c, c->rec_stage.grow(bytes));
     const int w = slot >= 0 ? slot : (which == P2PMG_REC_ACTION ? 5 : 6);
     const uint32_t tb = (uint32_t)(c->cfg.n_temp_states * c->cfg.n_balance_states);
-    HIP_TRY(c, p2pmg::launch_fast_rec_unpack(c->T, c->R + 1, c->A, tb, c->rec_pack, c->rec_narrow, w, c->rec_stage,
+    HIP_TRY(c, p2pmg::launch_fast_rec_unpack(c->T, c->R + 1, c->A, tb, c->rec_pack, c->last.narrow, w, c->rec_stage,
                                              c->stream));
     src = c->rec_stage;
   }
@@ -1127,8 +1070,8 @@ int p2pmg_get_record(p2pmg_ctx* c, int which, void* host) {
 int p2pmg_episode_summary(p2pmg_ctx* c, double* per_agent, double* per_scenario) {
   if (!c) return P2PMG_E_INVALID;
   if (!per_agent && !per_scenario) return fail(c, P2PMG_E_INVALID, "episode_summary: both outputs are null");
-  if (c->last_kernel.empty()) return fail(c, P2PMG_E_STATE, "episode_summary: no episode has run (cost, grid, p2p, t_in and action records are needed)");
-  const int missing = P2PMG_SUMMARY_RECORDS & ~c->rec_last_mask;
+  if (c->last.kernel.empty()) return fail(c, P2PMG_E_STATE, "episode_summary: no episode has run (cost, grid, p2p, t_in and action records are needed)");
+  const int missing = P2PMG_SUMMARY_RECORDS & ~c->last.mask;
   if (missing) {
     static const struct { int bit; const char* name; } names[] = {{P2PMG_REC_COST, "cost"}, {P2PMG_REC_GRID, "grid"},
                                                                   {P2PMG_REC_P2P, "p2p"}, {P2PMG_REC_TEMP, "t_in"},
@@ -1139,8 +1082,8 @@ int p2pmg_episode_summary(p2pmg_ctx* c, double* per_agent, double* per_scenario)
     return fail(c, P2PMG_E_STATE, "episode_summary: the last episode launch did not record " + list);
   }
   const size_t A = (size_t)c->A, S = (size_t)c->S;
-  if (!c->sum_agent) HIP_TRY(c, dmalloc(&c->sum_agent, A * P2PMG_SUMMARY_FIELDS));
-  if (!c->sum_scen) HIP_TRY(c, dmalloc(&c->sum_scen, S * P2PMG_SUMMARY_FIELDS));
+  if (!c->sum_agent) HIP_TRY(c, c->sum_agent.alloc(A * P2PMG_SUMMARY_FIELDS));
+  if (!c->sum_scen) HIP_TRY(c, c->sum_scen.alloc(S * P2PMG_SUMMARY_FIELDS));
   p2pmg::SummaryParams p{};
   p.S = c->S;
   p.N = c->N;
@@ -1149,8 +1092,8 @@ int p2pmg_episode_summary(p2pmg_ctx* c, double* per_agent, double* per_scenario)
   p.A = c->A;
   // a fast / sq16 launch packs every record it was asked for into rec_pack's rows (all of them here:
   // the narrow {reward, cost} form lacks the records checked above)
-  p.packed = (c->rec_fast_mask & P2PMG_SUMMARY_RECORDS) ? 1 : 0;
-  p.has_reward = (c->rec_last_mask & P2PMG_REC_REWARD) ? 1 : 0;
+  p.packed = (c->last.packed_mask & P2PMG_SUMMARY_RECORDS) ? 1 : 0;
+  p.has_reward = (c->last.mask & P2PMG_REC_REWARD) ? 1 : 0;
   p.reward = c->rec_f32[0];
   p.cost = c->rec_f32[1];
   p.grid = c->rec_f32[2];
@@ -1185,13 +1128,7 @@ int p2pmg_prepass_stats(p2pmg_ctx* c, int64_t* hits, int64_t* misses) {
 
 // device -> caller's host memory through the pinned staging buffer (stream-ordered, then synced)
 static int read_small(p2pmg_ctx* c, void* host, const void* dev, size_t bytes) {
-  if (c->h_small_bytes < bytes) {
-    if (c->h_small) (void)hipHostFree(c->h_small);
-    c->h_small = nullptr;
-    c->h_small_bytes = 0;
-    HIP_TRY(c, hipHostMalloc(&c->h_small, bytes, hipHostMallocDefault));
-    c->h_small_bytes = bytes;
-  }
+  HIP_TRY(c, c->h_small.grow(bytes));
   HIP_TRY(c, hipMemcpyAsync(c->h_small, dev, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   std::memcpy(host, c->h_small, bytes);
@@ -1207,8 +1144,8 @@ int p2pmg_rc_step(p2pmg_ctx* c, int n, const float* t_out, const float* t_in, co
                   float* t_in_new, float* t_m_new) {
   if (!c || n < 0 || !t_out || !t_in || !t_m || !hp || !t_in_new || !t_m_new) return P2PMG_E_INVALID;
   if (n == 0) return P2PMG_OK;
-  float* d = nullptr;
-  HIP_TRY(c, dmalloc(&d, (size_t)6 * n));
+  DevBuf<float> d;
+  HIP_TRY(c, d.alloc((size_t)6 * n));
   const size_t b = (size_t)n * 4;
   hipError_t e = hipMemcpyAsync(d, t_out, b, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d + n, t_in, b, hipMemcpyHostToDevice, c->stream);
@@ -1223,7 +1160,6 @@ int p2pmg_rc_step(p2pmg_ctx* c, int n, const float* t_out, const float* t_in, co
   if (e == hipSuccess) e = hipMemcpyAsync(t_in_new, d + 4 * (size_t)n, b, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(t_m_new, d + 5 * (size_t)n, b, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(d);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("rc_step: ") + hipGetErrorString(e));
   return P2PMG_OK;
 }
@@ -1232,8 +1168,8 @@ int p2pmg_rc_step_ex(p2pmg_ctx* c, int n, const float* t_out, const float* t_in,
                      const float* cop, float solar_gain, float* t_in_new, float* t_m_new) {
   if (!c || n < 0 || !t_out || !t_in || !t_m || !hp || !t_in_new || !t_m_new) return P2PMG_E_INVALID;
   if (n == 0) return P2PMG_OK;
-  float* d = nullptr;
-  HIP_TRY(c, dmalloc(&d, (size_t)7 * n));
+  DevBuf<float> d;
+  HIP_TRY(c, d.alloc((size_t)7 * n));
   const size_t b = (size_t)n * 4, sn = (size_t)n;
   hipError_t e = hipMemcpyAsync(d, t_out, b, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d + sn, t_in, b, hipMemcpyHostToDevice, c->stream);
@@ -1249,7 +1185,6 @@ int p2pmg_rc_step_ex(p2pmg_ctx* c, int n, const float* t_out, const float* t_in,
   if (e == hipSuccess) e = hipMemcpyAsync(t_in_new, d + 4 * sn, b, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(t_m_new, d + 5 * sn, b, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(d);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("rc_step_ex: ") + hipGetErrorString(e));
   return P2PMG_OK;
 }
@@ -1258,18 +1193,15 @@ extern "C++" template <typename T, typename L>
 static int div_check(p2pmg_ctx* c, int n, const T* a, const T* b, T* out, int per, L launch, const char* what) {
   if (!c || n < 0 || (n > 0 && (!a || !b || !out))) return P2PMG_E_INVALID;
   if (n == 0) return P2PMG_OK;
-  T *da = nullptr, *db = nullptr, *dout = nullptr;
-  hipError_t e = dmalloc(&da, (size_t)n);
-  if (e == hipSuccess) e = dmalloc(&db, (size_t)n);
-  if (e == hipSuccess) e = dmalloc(&dout, (size_t)n * per);
+  DevBuf<T> da, db, dout;
+  hipError_t e = da.alloc((size_t)n);
+  if (e == hipSuccess) e = db.alloc((size_t)n);
+  if (e == hipSuccess) e = dout.alloc((size_t)n * per);
   if (e == hipSuccess) e = hipMemcpyAsync(da, a, (size_t)n * sizeof(T), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(db, b, (size_t)n * sizeof(T), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = launch(n, da, db, dout, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n * per * sizeof(T), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(da);
-  dfree(db);
-  dfree(dout);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
   return P2PMG_OK;
 }
@@ -1285,10 +1217,10 @@ int p2pmg_fdiv64_check(p2pmg_ctx* c, int n, const double* a, const double* b, do
 int p2pmg_state_indices(p2pmg_ctx* c, int n, const float* obs, int32_t* idx) {
   if (!c || n < 0 || !obs || !idx) return P2PMG_E_INVALID;
   if (n == 0) return P2PMG_OK;
-  float* d = nullptr;
-  int32_t* di = nullptr;
-  HIP_TRY(c, dmalloc(&d, (size_t)4 * n));
-  hipError_t e = dmalloc(&di, (size_t)4 * n);
+  DevBuf<float> d;
+  DevBuf<int32_t> di;
+  HIP_TRY(c, d.alloc((size_t)4 * n));
+  hipError_t e = di.alloc((size_t)4 * n);
   if (e == hipSuccess) e = hipMemcpyAsync(d, obs, (size_t)16 * n, hipMemcpyHostToDevice, c->stream);
   const p2pmg_config& g = c->cfg;
   if (e == hipSuccess)
@@ -1296,8 +1228,6 @@ int p2pmg_state_indices(p2pmg_ctx* c, int n, const float* obs, int32_t* idx) {
                                     c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(idx, di, (size_t)16 * n, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(d);
-  dfree(di);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("state_indices: ") + hipGetErrorString(e));
   return P2PMG_OK;
 }
@@ -1370,7 +1300,7 @@ int p2pmg_set_battery(p2pmg_ctx* c, const double* capacity, double min_soc, doub
   }
   if (!(efficiency > 0.0) || !(min_soc <= max_soc)) return fail(c, P2PMG_E_INVALID, "set_battery: bad parameters");
   const size_t A = (size_t)c->A;
-  if (!c->bat_cap) HIP_TRY(c, dmalloc(&c->bat_cap, A));
+  if (!c->bat_cap) HIP_TRY(c, c->bat_cap.alloc(A));
   HIP_TRY(c, hipMemcpyAsync(c->bat_cap, capacity, A * 8, hipMemcpyHostToDevice, c->stream));
   std::vector<double> s0(A, 0.5);
   HIP_TRY(c, hipMemcpyAsync(c->soc, soc0 ? soc0 : s0.data(), A * 8, hipMemcpyHostToDevice, c->stream));
@@ -1403,8 +1333,8 @@ int p2pmg_battery_seq(p2pmg_ctx* c, int agents, int steps, const double* bal, do
                       double* soc, const double* cap, double smin, double smax, double eff) {
   if (!c || agents < 0 || steps < 0 || !bal || !out_bal || !soc_hist || !soc || !cap) return P2PMG_E_INVALID;
   const size_t n = (size_t)agents * steps;
-  double* d = nullptr;
-  HIP_TRY(c, dmalloc(&d, 3 * n + 2 * (size_t)agents + 1));
+  DevBuf<double> d;
+  HIP_TRY(c, d.alloc(3 * n + 2 * (size_t)agents + 1));
   double *db = d, *dob = d + n, *dsh = d + 2 * n, *ds = d + 3 * n, *dc = d + 3 * n + agents;
   hipError_t e = hipMemcpyAsync(db, bal, n * 8, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(ds, soc, (size_t)agents * 8, hipMemcpyHostToDevice, c->stream);
@@ -1415,7 +1345,6 @@ int p2pmg_battery_seq(p2pmg_ctx* c, int agents, int steps, const double* bal, do
   if (e == hipSuccess) e = hipMemcpyAsync(soc_hist, dsh, n * 8, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(soc, ds, (size_t)agents * 8, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(d);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("battery_seq: ") + hipGetErrorString(e));
   return P2PMG_OK;
 }
@@ -1480,27 +1409,20 @@ int p2pmg_comm_init(p2pmg_ctx* c, const uint8_t id[128], int rank, int nranks) {
 // HIP events around each data-path all-reduce (shared-table delta, DQN gradient), on the context's
 // stream, so the bench line can report what the exchange step costs at world > 1
 static hipError_t coll_mark(p2pmg_ctx* c, int end) {
-  if (c->cring.empty()) {
-    c->cring.assign(2 * p2pmg_ctx::kCRing, nullptr);
-    for (auto& ev : c->cring) {
-      const hipError_t e = hipEventCreate(&ev);
-      if (e != hipSuccess) return e;
-    }
-  }
-  const int slot = (int)(c->n_coll % p2pmg_ctx::kCRing);
+  hipError_t e = c->cring.ensure(p2pmg_ctx::kCRing);
+  if (e != hipSuccess) return e;
   if (!end && c->n_coll >= p2pmg_ctx::kCRing && c->n_coll_folded == c->n_coll - p2pmg_ctx::kCRing) {
     // the slot's previous pair (kCRing collectives ago) is about to be overwritten: fold its
     // duration into the running total first, so p2pmg_collective_ms counts every collective.
     // Once per collective: a start whose collective then failed (no end mark, n_coll unchanged)
     // is followed by another start on the same slot, which must not fold the slot again
     float ms = 0.0f;
-    hipError_t e = hipEventSynchronize(c->cring[2 * slot + 1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->cring[2 * slot], c->cring[2 * slot + 1]);
+    e = c->cring.elapsed(c->n_coll, &ms);
     if (e != hipSuccess) return e;
     c->coll_folded_ms += ms;
     c->n_coll_folded++;
   }
-  const hipError_t e = hipEventRecord(c->cring[2 * slot + end], c->stream);
+  e = hipEventRecord(c->cring.pair(c->n_coll)[end], c->stream);
   if (end) c->n_coll++;
   return e;
 }
@@ -1510,10 +1432,8 @@ int p2pmg_collective_ms(p2pmg_ctx* c, double* total_ms, int* count) {
   const long long n = c->n_coll < p2pmg_ctx::kCRing ? c->n_coll : p2pmg_ctx::kCRing;
   double sum = 0.0;
   for (long long k = c->n_coll - n; k < c->n_coll; ++k) {
-    const int slot = (int)(k % p2pmg_ctx::kCRing);
     float ms = 0.0f;
-    HIP_TRY(c, hipEventSynchronize(c->cring[2 * slot + 1]));
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->cring[2 * slot], c->cring[2 * slot + 1]));
+    HIP_TRY(c, c->cring.elapsed(k, &ms));
     sum += ms;
   }
   *total_ms = c->coll_folded_ms + sum;
@@ -1551,7 +1471,7 @@ int p2pmg_comm_nranks(p2pmg_ctx* c, int* n) {
 int p2pmg_allreduce_metrics(p2pmg_ctx* c, double* out) {
   if (!c || !out) return P2PMG_E_INVALID;
   if (!c->ep_reward) return fail(c, P2PMG_E_STATE, "allreduce_metrics: no episode launched");
-  if (!c->d_metrics) HIP_TRY(c, dmalloc(&c->d_metrics, 2));
+  if (!c->d_metrics) HIP_TRY(c, c->d_metrics.alloc(2));
   HIP_TRY(c, p2pmg::launch_metrics(c->S, c->ep_reward, c->d_metrics, c->stream));
   if (c->comm) {  // ncclFloat64 = 8, ncclSum = 0: sum and count over every rank (xGMI)
     Rccl* r = rccl();
@@ -1566,7 +1486,7 @@ int p2pmg_table_hash_allgather(p2pmg_ctx* c, uint64_t* out) {
   if (!c->q || c->n_tables == 0) return fail(c, P2PMG_E_STATE, "table_hash: context has no Q-table");
   const int n = c->comm ? c->nranks : 1;
   if (n > 1024) return fail(c, P2PMG_E_UNSUPPORTED, "table_hash: more than 1024 ranks");
-  if (!c->d_hash) HIP_TRY(c, dmalloc(&c->d_hash, 1025));
+  if (!c->d_hash) HIP_TRY(c, c->d_hash.alloc(1025));
   const size_t bytes = c->n_tables * c->n_states * kQPad * c->q_elem;
   HIP_TRY(c, p2pmg::launch_table_hash(c->q, bytes, c->d_hash + 1024, c->stream));
   if (c->comm) {  // ncclUint64 = 5: every rank's fingerprint, in rank order
@@ -1603,8 +1523,8 @@ int p2pmg_q_calls(p2pmg_ctx* c, int n, const int32_t* agents, const float* s_obs
   const size_t off_s = 0, off_ns = off_s + 16 * nb, off_r = off_ns + 16 * nb, off_a = off_r + 4 * nb,
                off_act = off_a + 4 * nb, off_q = ((off_act + 4 * nb + 7) / 8) * 8, off_c = off_q + 8 * nb,
                total = off_c + nb;
-  char* d = nullptr;
-  HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d), total));
+  DevBuf<char> d;
+  HIP_TRY(c, d.alloc(total));
   hipError_t e = hipMemcpyAsync(d + off_s, s_obs, 16 * nb, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess && train) e = hipMemcpyAsync(d + off_ns, ns_obs, 16 * nb, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess && train) e = hipMemcpyAsync(d + off_r, rewards, 4 * nb, hipMemcpyHostToDevice, c->stream);
@@ -1621,7 +1541,6 @@ int p2pmg_q_calls(p2pmg_ctx* c, int n, const int32_t* agents, const float* s_obs
   if (e == hipSuccess) e = hipMemcpyAsync(actions_out, d + off_act, 4 * nb, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(q_out, d + off_q, 8 * nb, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("q_calls: ") + hipGetErrorString(e));
   return P2PMG_OK;
 }
@@ -1680,11 +1599,9 @@ int p2pmg_dqn_setup(p2pmg_ctx* c, const p2pmg_dqn_config* cfg) {
   const size_t A = (size_t)c->A, NS = p2pmg::kNetStride;
   c->n_nets = c->cfg.shared_q ? 1 : c->A;
   const size_t nn = (size_t)c->n_nets * NS;
-  HIP_TRY(c, dmalloc(&c->d_theta, nn));
-  HIP_TRY(c, dmalloc(&c->d_target, nn));
-  HIP_TRY(c, dmalloc(&c->d_m, nn));
-  HIP_TRY(c, dmalloc(&c->d_v, nn));
-  for (float* b : {c->d_theta, c->d_target, c->d_m, c->d_v}) HIP_TRY(c, hipMemsetAsync(b, 0, nn * 4, c->stream));
+  for (DevBuf<float>* b : {&c->d_theta, &c->d_target, &c->d_m, &c->d_v}) HIP_TRY(c, b->alloc(nn));
+  for (DevBuf<float>* b : {&c->d_theta, &c->d_target, &c->d_m, &c->d_v})
+    HIP_TRY(c, hipMemsetAsync(b->get(), 0, nn * 4, c->stream));
   if (cfg->agents_per_block < 0 || cfg->grad_segments < 0) return fail(c, P2PMG_E_INVALID, "dqn_setup: negative layout");
   if (c->cfg.shared_q) {
     // gradient segments: contiguous runs of whole scenarios; the train workgroups never straddle two
@@ -1698,8 +1615,8 @@ int p2pmg_dqn_setup(p2pmg_ctx* c, const p2pmg_dqn_config* cfg) {
     c->d_apb = apb < 1 ? 1 : apb;
     c->d_bps = (c->d_seg_agents + c->d_apb - 1) / c->d_apb;
     c->d_blocks = G * c->d_bps;
-    HIP_TRY(c, dmalloc(&c->d_grad, (size_t)c->d_blocks * NS));
-    HIP_TRY(c, dmalloc(&c->d_alt, 4 * NS));
+    HIP_TRY(c, c->d_grad.alloc((size_t)c->d_blocks * NS));
+    HIP_TRY(c, c->d_alt.alloc(4 * NS));
   } else {
     c->d_apb = 1;
     c->d_blocks = c->A;
@@ -1707,11 +1624,11 @@ int p2pmg_dqn_setup(p2pmg_ctx* c, const p2pmg_dqn_config* cfg) {
     c->d_seg_agents = c->A;
     c->d_bps = c->A;
   }
-  HIP_TRY(c, dmalloc(&c->d_buf, A * (size_t)cfg->capacity * p2pmg::kTrans));
-  HIP_TRY(c, dmalloc(&c->d_added, A));
-  HIP_TRY(c, dmalloc(&c->d_smp, A * p2pmg::kDqnBatch));
+  HIP_TRY(c, c->d_buf.alloc(A * (size_t)cfg->capacity * p2pmg::kTrans));
+  HIP_TRY(c, c->d_added.alloc(A));
+  HIP_TRY(c, c->d_smp.alloc(A * p2pmg::kDqnBatch));
   HIP_TRY(c, hipMemsetAsync(c->d_added, 0, A * 4, c->stream));
-  HIP_TRY(c, dmalloc(&c->d_ep_acc, (size_t)c->S));
+  HIP_TRY(c, c->d_ep_acc.alloc((size_t)c->S));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->d_steps.assign((size_t)c->n_nets, 0);
   c->d_added_min = 0;
@@ -1735,8 +1652,7 @@ static int dqn_ready(p2pmg_ctx* c, const char* what) {
 }
 
 int p2pmg_dqn_set_weights(p2pmg_ctx* c, int which, int first, int count, const float* host) {
-  int rc = dqn_ready(c, "dqn_set_weights");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_set_weights"));
   float* dst = dqn_array(c, which);
   if (!dst || !host || first < 0 || count < 0 || first + count > c->n_nets)
     return fail(c, P2PMG_E_INVALID, "dqn_set_weights: bad array/range");
@@ -1747,8 +1663,7 @@ int p2pmg_dqn_set_weights(p2pmg_ctx* c, int which, int first, int count, const f
 }
 
 int p2pmg_dqn_get_weights(p2pmg_ctx* c, int which, int first, int count, float* host) {
-  int rc = dqn_ready(c, "dqn_get_weights");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_get_weights"));
   const float* src = dqn_array(c, which);
   if (!src || !host || first < 0 || count < 0 || first + count > c->n_nets)
     return fail(c, P2PMG_E_INVALID, "dqn_get_weights: bad array/range");
@@ -1759,35 +1674,31 @@ int p2pmg_dqn_get_weights(p2pmg_ctx* c, int which, int first, int count, float* 
 }
 
 int p2pmg_dqn_set_step(p2pmg_ctx* c, int64_t step) {
-  int rc = dqn_ready(c, "dqn_set_step");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_set_step"));
   if (step < 0) return P2PMG_E_INVALID;
   std::fill(c->d_steps.begin(), c->d_steps.end(), step);  // every network
   return P2PMG_OK;
 }
 
 int p2pmg_dqn_get_step(p2pmg_ctx* c, int64_t* step) {
-  int rc = dqn_ready(c, "dqn_get_step");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_get_step"));
   if (!step) return P2PMG_E_INVALID;
   *step = c->d_steps[0];
   return P2PMG_OK;
 }
 
 int p2pmg_dqn_get_net_steps(p2pmg_ctx* c, int first, int count, int64_t* steps) {
-  int rc = dqn_ready(c, "dqn_get_net_steps");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_get_net_steps"));
   if (!steps || first < 0 || count < 0 || first + count > c->n_nets) return fail(c, P2PMG_E_INVALID, "dqn_get_net_steps");
   for (int k = 0; k < count; ++k) steps[k] = c->d_steps[(size_t)first + k];
   return P2PMG_OK;
 }
 
 int p2pmg_dqn_set_samples(p2pmg_ctx* c, const uint16_t* samples) {
-  int rc = dqn_ready(c, "dqn_set_samples");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_set_samples"));
   if (!samples) return P2PMG_E_INVALID;
   const size_t n = (size_t)c->T * c->A * p2pmg::kDqnBatch;
-  if (!c->d_samples) HIP_TRY(c, dmalloc(&c->d_samples, n));
+  if (!c->d_samples) HIP_TRY(c, c->d_samples.alloc(n));
   HIP_TRY(c, hipMemcpyAsync(c->d_samples, samples, n * 2, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->have_samples = true;
@@ -1805,8 +1716,7 @@ static int dqn_refresh_added_min(p2pmg_ctx* c) {
 }
 
 int p2pmg_dqn_get_buffer(p2pmg_ctx* c, int first, int count, float* host, int32_t* added) {
-  int rc = dqn_ready(c, "dqn_get_buffer");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_get_buffer"));
   if (first < 0 || count < 0 || first + count > c->A) return fail(c, P2PMG_E_INVALID, "dqn_get_buffer: range");
   const size_t per = (size_t)c->dcfg.capacity * p2pmg::kTrans;
   if (host)
@@ -1819,8 +1729,7 @@ int p2pmg_dqn_get_buffer(p2pmg_ctx* c, int first, int count, float* host, int32_
 }
 
 int p2pmg_dqn_set_buffer(p2pmg_ctx* c, int first, int count, const float* host, const int32_t* added) {
-  int rc = dqn_ready(c, "dqn_set_buffer");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_set_buffer"));
   if (first < 0 || count < 0 || first + count > c->A) return fail(c, P2PMG_E_INVALID, "dqn_set_buffer: range");
   const size_t per = (size_t)c->dcfg.capacity * p2pmg::kTrans;
   if (host)
@@ -1902,13 +1811,7 @@ static bool dqn_steps_same(const p2pmg_ctx* c) {
 // up front: one [T][n_nets] table, uploaded once per episode (not a copy + sync per env step).
 static int dqn_upload_lr_table(p2pmg_ctx* c) {
   const size_t n = c->d_steps.size(), need = (size_t)c->T * n;
-  if (c->d_lr_cap < need) {
-    dfree(c->d_lr);
-    c->d_lr = nullptr;
-    c->d_lr_cap = 0;
-    HIP_TRY(c, dmalloc(&c->d_lr, need));
-    c->d_lr_cap = need;
-  }
+  HIP_TRY(c, c->d_lr.grow(need));
   c->h_lr.resize(need);
   for (int t = 0; t < c->T; ++t)
     for (size_t k = 0; k < n; ++k) c->h_lr[(size_t)t * n + k] = adam_lr(c->dcfg, c->d_steps[k] + 1 + t);
@@ -1921,19 +1824,8 @@ static int dqn_upload_lr_table(p2pmg_ctx* c) {
 // allocated for the current world (comm_init / set_exchange may come after dqn_setup)
 static int dqn_ensure_segs(p2pmg_ctx* c, p2pmg::DqnParams& d) {
   const size_t need = (size_t)c->nranks * c->d_seg_local * p2pmg::kNetStride;
-  if (c->d_segs_cap < need) {
-    dfree(c->d_segs);
-    c->d_segs_cap = 0;
-    HIP_TRY(c, dmalloc(&c->d_segs, need));
-    c->d_segs_cap = need;
-  }
-  if (c->xfn && !c->comm && c->h_segs_cap < need) {
-    if (c->h_segs) (void)hipHostFree(c->h_segs);
-    c->h_segs = nullptr;
-    c->h_segs_cap = 0;
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_segs), need * 4, hipHostMallocDefault));
-    c->h_segs_cap = need;
-  }
+  HIP_TRY(c, c->d_segs.grow(need));
+  if (c->xfn && !c->comm) HIP_TRY(c, c->h_segs.grow(need));
   d.segs = c->d_segs;
   d.seg_first = c->rank * c->d_seg_local;
   d.n_segs = c->nranks * c->d_seg_local;
@@ -1981,8 +1873,7 @@ static int dqn_train_step(p2pmg_ctx* c, p2pmg::DqnParams& d, bool same, bool def
     } else {
       HIP_TRY(c, p2pmg::launch_dqn_reduce_adam(d, c->d_seg_local, false, c->stream));
       if (c->nranks > 1 || c->comm) {  // a communicator gathers even at world 1 (the RCCL path, tested)
-        const int rc = dqn_gather_segments(c);
-        if (rc != P2PMG_OK) return rc;
+        RC_TRY(dqn_gather_segments(c));
       }
       if (defer) d.adam_pending = 1;
       else HIP_TRY(c, p2pmg::launch_dqn_adam_shared(d, c->stream));
@@ -1995,9 +1886,7 @@ static int dqn_train_step(p2pmg_ctx* c, p2pmg::DqnParams& d, bool same, bool def
 }
 
 static int dqn_run_episode(p2pmg_ctx* c, const p2pmg_episode_args* args) {
-  c->rec_fast_mask = 0;
-  int rc = dqn_ready(c, "run_episode");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "run_episode"));
   const int mode = args->mode;
   if (mode != P2PMG_MODE_TRAIN && mode != P2PMG_MODE_GREEDY && mode != P2PMG_MODE_FILL)
     return fail(c, P2PMG_E_INVALID, "mode");
@@ -2010,19 +1899,13 @@ static int dqn_run_episode(p2pmg_ctx* c, const p2pmg_episode_args* args) {
   if (mode == P2PMG_MODE_TRAIN && c->d_added_min + 1 < p2pmg::kDqnBatch)
     return fail(c, P2PMG_E_STATE, "run_episode: fill the replay memory first (>= 31 transitions per agent, "
                                   "community.init_buffers)");
-  rc = ensure_records(c, args->record);
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(ensure_records(c, args->record));
   EpisodeParams e = episode_params(c, args);
   e.rng = (acting && args->rng == P2PMG_RNG_PHILOX) ? 1 : 0;
   p2pmg::DqnParams d = dqn_params(c, e);
   if (mode == P2PMG_MODE_TRAIN && args->rng == P2PMG_RNG_REPLAY) d.samples = c->d_samples;
   if (mode == P2PMG_MODE_TRAIN && c->n_nets == 1 && (c->nranks > 1 || c->d_seg_local > 1)) {
-    rc = dqn_ensure_segs(c, d);
-    if (rc != P2PMG_OK) return rc;
-  }
-  if (c->ring.empty()) {
-    c->ring.assign(2 * p2pmg_ctx::kRing, nullptr);
-    for (auto& ev : c->ring) HIP_TRY(c, hipEventCreate(&ev));
+    RC_TRY(dqn_ensure_segs(c, d));
   }
   d.fused_sample = (mode == P2PMG_MODE_TRAIN) ? 1 : 0;  // the act launch of each env step draws the samples
   {  // P2PMG_DQN_ACT=wave: the one-wave-per-agent act kernel for a shared network too (tests, A/B)
@@ -2036,12 +1919,9 @@ static int dqn_run_episode(p2pmg_ctx* c, const p2pmg_episode_args* args) {
     const char* at = getenv("P2PMG_ADAM_TPB");  // post-exchange Adam workgroup size: 64, 128, 256 (default)
     d.adam_tpb = at ? atoi(at) : 256;
   }
-  c->last_kernel = std::string(c->n_nets == 1 && !d.act_wave ? "dqn_act_shared_kernel<" : "dqn_act_kernel<") +
-                   std::to_string(c->N) + ">";
   const bool same = mode != P2PMG_MODE_TRAIN || dqn_steps_same(c);
   if (!same) {
-    rc = dqn_upload_lr_table(c);
-    if (rc != P2PMG_OK) return rc;
+    RC_TRY(dqn_upload_lr_table(c));
   }
   // The shared network's split path (segments / ranks): env step t's post-exchange Adam step runs
   // inside env step t + 1's act launch, which reads the state from one half of a double buffer and
@@ -2070,8 +1950,8 @@ static int dqn_run_episode(p2pmg_ctx* c, const p2pmg_episode_args* args) {
     dqn_bind(d, prim, prim);
     return P2PMG_OK;
   };
-  const int slot = (int)(c->n_timed % p2pmg_ctx::kRing);
-  HIP_TRY(c, hipEventRecord(c->ring[2 * slot], c->stream));
+  Timed tm;
+  RC_TRY(begin_timed(c, false, true, &tm));
   // Philox training: every env step's replay draws in one throughput launch ahead of the episode,
   // read by the act launches like uploaded samples (P2PMG_DQN_SAMPLE_PREPASS=0: drawn in each act
   // launch's tail, as the episode's first form did)
@@ -2080,7 +1960,7 @@ static int dqn_run_episode(p2pmg_ctx* c, const p2pmg_episode_args* args) {
     const bool no_px = px_env && !strcmp(px_env, "0");
     const size_t n = (size_t)c->T * c->A * p2pmg::kDqnBatch;
     if (mode == P2PMG_MODE_TRAIN && args->rng == P2PMG_RNG_PHILOX && !no_px && n <= ((size_t)1 << 30)) {
-      if (!c->d_samples_px) HIP_TRY(c, dmalloc(&c->d_samples_px, n));
+      if (!c->d_samples_px) HIP_TRY(c, c->d_samples_px.alloc(n));
       HIP_TRY(c, p2pmg::launch_dqn_sample_prepass(d, c->d_samples_px, c->stream));
       d.samples = c->d_samples_px;
     }
@@ -2100,48 +1980,42 @@ static int dqn_run_episode(p2pmg_ctx* c, const p2pmg_episode_args* args) {
       dqn_bind(d, on_alt ? alt : prim, on_alt ? alt : prim);
     }
     if (mode == P2PMG_MODE_TRAIN) {
-      rc = dqn_train_step(c, d, same, defer);
+      const int rc = dqn_train_step(c, d, same, defer);
       if (rc != P2PMG_OK) {
         (void)settle();
         return rc;
       }
     }
   }
-  rc = settle();
-  if (rc != P2PMG_OK) return rc;
-  HIP_TRY(c, hipEventRecord(c->ring[2 * slot + 1], c->stream));
-  c->timed = true;
-  c->n_timed++;
-  c->rec_last_mask = args->record;
+  RC_TRY(settle());
+  RC_TRY(end_timed(c, tm, true));
+  finish_launch(c, tm, std::string(c->n_nets == 1 && !d.act_wave ? "dqn_act_shared_kernel<" : "dqn_act_kernel<") +
+                           std::to_string(c->N) + ">", args->record, 0, 0);
   if (acting) c->d_added_min += c->T;
   if (acting && args->rng == P2PMG_RNG_REPLAY) c->have_codes = c->code_src == 1;
   return P2PMG_OK;
 }
 
 int p2pmg_dqn_forward(p2pmg_ctx* c, int net, int n, const float* x, float* q) {
-  int rc = dqn_ready(c, "dqn_forward");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_forward"));
   if (net < 0 || net >= c->n_nets || n < 0 || (n > 0 && (!x || !q))) return fail(c, P2PMG_E_INVALID, "dqn_forward");
   if (n == 0) return P2PMG_OK;
-  float *dx = nullptr, *dq = nullptr;
-  HIP_TRY(c, dmalloc(&dx, (size_t)n * 5));
-  hipError_t e = dmalloc(&dq, (size_t)n);
+  DevBuf<float> dx, dq;
+  HIP_TRY(c, dx.alloc((size_t)n * 5));
+  hipError_t e = dq.alloc((size_t)n);
   if (e == hipSuccess) e = hipMemcpyAsync(dx, x, (size_t)n * 20, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = p2pmg::launch_dqn_forward(c->d_theta + (size_t)net * p2pmg::kNetStride, n, dx, dq, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(q, dq, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(dx);
-  dfree(dq);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("dqn_forward: ") + hipGetErrorString(e));
   return P2PMG_OK;
 }
 
 int p2pmg_dqn_train_batch(p2pmg_ctx* c, int net, const float* batch, float* loss) {
-  int rc = dqn_ready(c, "dqn_train_batch");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_train_batch"));
   if (net < 0 || net >= c->n_nets || !batch) return fail(c, P2PMG_E_INVALID, "dqn_train_batch");
-  float* db = nullptr;
-  HIP_TRY(c, dmalloc(&db, (size_t)p2pmg::kDqnBatch * p2pmg::kTrans + 1));
+  DevBuf<float> db;
+  HIP_TRY(c, db.alloc((size_t)p2pmg::kDqnBatch * p2pmg::kTrans + 1));
   p2pmg_episode_args args{P2PMG_MODE_TRAIN, P2PMG_RNG_PHILOX, 0, 0, 0.0, 0, 0};
   p2pmg::DqnParams d = dqn_params(c, episode_params(c, &args));
   d.batch = db;
@@ -2153,7 +2027,6 @@ int p2pmg_dqn_train_batch(p2pmg_ctx* c, int net, const float* batch, float* loss
   float l = 0.0f;
   if (e == hipSuccess) e = hipMemcpyAsync(&l, d.loss_out, 4, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(db);
   if (e != hipSuccess) return fail(c, P2PMG_E_HIP, std::string("dqn_train_batch: ") + hipGetErrorString(e));
   if (loss) *loss = l;
   return P2PMG_OK;
@@ -2178,8 +2051,7 @@ int p2pmg_dqn_set_exchange(p2pmg_ctx* c, p2pmg_exchange_fn fn, void* user, int r
 }
 
 int p2pmg_dqn_grad_layout(p2pmg_ctx* c, int* segments, int* agents_per_block, int* blocks) {
-  int rc = dqn_ready(c, "dqn_grad_layout");
-  if (rc != P2PMG_OK) return rc;
+  RC_TRY(dqn_ready(c, "dqn_grad_layout"));
   if (segments) *segments = c->d_seg_local;
   if (agents_per_block) *agents_per_block = c->d_apb;
   if (blocks) *blocks = c->d_blocks;
