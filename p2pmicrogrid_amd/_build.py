@@ -17,9 +17,29 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libp2pmg.so")
-SOURCES = ["p2pmg_kernels.hip", "p2pmg_dqn.hip", "p2pmg_summary.hip", "p2pmg_runtime.cpp", "p2pmg_plan.cpp"]
-HEADERS = ["p2pmg_internal.h", "p2pmg_device.h", "p2pmg_plan.h", os.path.join(ROOT, "include", "p2pmg.h")]
+HEADERS = ["p2pmg_internal.h", "p2pmg_device.h", "p2pmg_tabular.h", "p2pmg_fastmath.h", "p2pmg_plan.h",
+           os.path.join(ROOT, "include", "p2pmg.h")]
 ARCH = os.environ.get("P2PMG_ARCH", "gfx950")
+
+# episode_sq16_kernel (VALU-issue-bound) without the SLP vectorizer:
+# SLP packs adjacent f32 adds / muls into v_pk_add_f32 / v_pk_mul_f32, which issue at 6.6 SIMD cycles
+# against 2 x 2.9 / 2 x 2.6 for the scalar pair at 4 waves per SIMD (profiles/r04_ubench_rate.jsonl);
+# the kernel's explicit packed FMAs (v_pk_fma_f32, 6.8 against 2 x 3.8) stay.  configs[2] 3.18 ->
+# 3.07 ms; the latency-bound fast kernel (other units) measured slower without SLP
+# (profiles/r04_sq16_slp_ab.txt).
+SQ16_FLAGS = ["-fno-slp-vectorize"]
+# The translation units: (source, slice define, extra flags, object name).  The fast and general episode
+# kernels are large sets of template instantiations, compiled in slices (see the tail of each file).
+UNITS = [
+    ("p2pmg_small.hip", None, [], "small.o"),
+    *[("p2pmg_fast.hip", f"P2PMG_FAST_SLICE={k}", [], f"fast_{k}.o") for k in range(4)],
+    ("p2pmg_sq16.hip", None, SQ16_FLAGS, "sq16.o"),
+    *[("p2pmg_general.hip", f"P2PMG_GENERAL_SLICE={k}", [], f"general_{k}.o") for k in range(9)],
+    ("p2pmg_dqn.hip", None, [], "p2pmg_dqn.o"),
+    ("p2pmg_summary.hip", None, [], "p2pmg_summary.o"),
+    ("p2pmg_runtime.cpp", None, [], "p2pmg_runtime.o"),
+    ("p2pmg_plan.cpp", None, [], "p2pmg_plan.o"),
+]
 
 
 def hipcc() -> str:
@@ -33,27 +53,15 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [h if os.path.isabs(h) else os.path.join(CSRC, h)
+    deps = [os.path.join(CSRC, u[0]) for u in UNITS] + [h if os.path.isabs(h) else os.path.join(CSRC, h)
                                                          for h in HEADERS]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
-
-
-KERNEL_PARTS = 15  # p2pmg_kernels.hip is compiled once per part (-DP2PMG_PART=k), see its header
-# Per-part compiler flags.  Part 5 (episode_sq16_kernel, VALU-issue-bound) without the SLP vectorizer:
-# SLP packs adjacent f32 adds / muls into v_pk_add_f32 / v_pk_mul_f32, which issue at 6.6 SIMD cycles
-# against 2 x 2.9 / 2 x 2.6 for the scalar pair at 4 waves per SIMD (profiles/r04_ubench_rate.jsonl);
-# the kernel's explicit packed FMAs (v_pk_fma_f32, 6.8 against 2 x 3.8) stay.  configs[2] 3.18 ->
-# 3.07 ms; the latency-bound fast kernel (other parts) measured slower without SLP
-# (profiles/r04_sq16_slp_ab.txt).
-PART_FLAGS = {5: ["-fno-slp-vectorize"]}
 
 
 def build(force: bool = False, verbose: bool = True, out: str = LIB, defines=(), jobs: int = 0) -> str:
     """defines: extra -D flags, or raw compiler flags when they start with "-" (timing-only ablation
     builds go to a different ``out``).
-    The translation units (15 parts of p2pmg_kernels.hip, p2pmg_dqn.hip, p2pmg_summary.hip, p2pmg_runtime.cpp,
-    p2pmg_plan.cpp) compile
-    in parallel into build/obj/<tag>/, then link into one shared library.  An exclusive file lock
+    The translation units (UNITS) compile in parallel into build/obj/<tag>/, then link into one shared library.  An exclusive file lock
     per tag serialises concurrent builders (torchrun ranks, pytest-xdist workers that all find the
     sources newer): the later ones wait, see a fresh library and return without compiling."""
     if out == LIB and not defines and not force and not needs_build():
@@ -84,9 +92,7 @@ def _build_locked(obj_dir: str, out: str, defines, jobs: int, verbose: bool, for
     common = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
               "-Wall", "-Wno-unused-function", "-Wno-pass-failed", f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}",
               *[d if d.startswith("-") else f"-D{d}" for d in defines]]  # "-..." entries: raw flags
-    units = [(os.path.join(CSRC, "p2pmg_kernels.hip"), [f"-DP2PMG_PART={k}", *PART_FLAGS.get(k, [])], f"kernels_{k}.o")
-             for k in range(KERNEL_PARTS)]
-    units += [(os.path.join(CSRC, s), [], os.path.splitext(s)[0] + ".o") for s in SOURCES if s != "p2pmg_kernels.hip"]
+    units = [(os.path.join(CSRC, s), [*([f"-D{d}"] if d else []), *flags], o) for s, d, flags, o in UNITS]
     jobs = jobs or min(len(units), max(1, int(os.environ.get("MAX_JOBS", os.cpu_count() or 4))))
     pending = list(units)
     running = []

@@ -1,4 +1,5 @@
-// Internal declarations shared by p2pmg_kernels.hip (device code + launchers) and
+// Internal declarations shared by the kernel units (device code + launchers: p2pmg_general.hip,
+// p2pmg_fast.hip, p2pmg_sq16.hip, p2pmg_small.hip, p2pmg_dqn.hip, p2pmg_summary.hip) and
 // p2pmg_runtime.cpp (context, C ABI).  Not part of the public ABI (include/p2pmg.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -188,24 +189,26 @@ hipError_t launch_step_prepass(const EpisodeParams& p, const PrepOut& o, hipStre
 // ev0 / ev1: timing events stamped by the dispatch (hipExtLaunchKernel)
 hipError_t launch_episode_fast(const EpisodeParams& p, const uint2* pre, void* recs, int q_dtype, int spw,
                                const PrepOut* next, hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream);
-// the per-part launchers behind launch_episode_fast / launch_episode (p2pmg_kernels.hip, P2PMG_PART)
-#define P2PMG_DECL_FAST_PART(k)                                                                               \
-  hipError_t launch_fast_part##k(const EpisodeParams& p, const uint2* pre, void* recs, int q_dtype, int spw, \
-                                 const PrepOut* next, hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream);
-P2PMG_DECL_FAST_PART(1)
-P2PMG_DECL_FAST_PART(2)
-P2PMG_DECL_FAST_PART(3)
-P2PMG_DECL_FAST_PART(4)
-hipError_t launch_general_part6(const EpisodeParams& p, int q_dtype, hipStream_t stream);
-hipError_t launch_general_part7(const EpisodeParams& p, int q_dtype, hipStream_t stream);
-hipError_t launch_general_part8(const EpisodeParams& p, int q_dtype, hipStream_t stream);
-hipError_t launch_tile_part9(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
-hipError_t launch_tile_part10(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
+// the slice launchers behind launch_episode_fast (p2pmg_fast.hip, one per P2PMG_FAST_SLICE; N = 1-2 / 3-4 /
+// 5-6 / 7-8) and launch_episode (p2pmg_general.hip, one per P2PMG_GENERAL_SLICE)
+#define P2PMG_DECL_FAST(name)                                                                                     \
+  hipError_t name(const EpisodeParams& p, const uint2* pre, void* recs, int q_dtype, int spw, const PrepOut* next, \
+                  hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream);
+P2PMG_DECL_FAST(launch_fast_n12)
+P2PMG_DECL_FAST(launch_fast_n34)
+P2PMG_DECL_FAST(launch_fast_n56)
+P2PMG_DECL_FAST(launch_fast_n78)
+// N compiled in (registers), then the LDS-tile form for up to nc = 16 / 32 and 64 agents
+hipError_t launch_general_n1_4(const EpisodeParams& p, int q_dtype, hipStream_t stream);
+hipError_t launch_general_n5_8(const EpisodeParams& p, int q_dtype, hipStream_t stream);
+hipError_t launch_general_n16(const EpisodeParams& p, int q_dtype, hipStream_t stream);
+hipError_t launch_general_tile16(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
+hipError_t launch_general_tile32_64(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
 // per-role tables (p.shared_q == 2); nc = 0: the register form
-hipError_t launch_role_part11(const EpisodeParams& p, int q_dtype, hipStream_t stream);
-hipError_t launch_role_part12(const EpisodeParams& p, int q_dtype, hipStream_t stream);
-hipError_t launch_role_part13(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
-hipError_t launch_role_part14(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
+hipError_t launch_role_n1_4(const EpisodeParams& p, int q_dtype, hipStream_t stream);
+hipError_t launch_role_n5_8(const EpisodeParams& p, int q_dtype, hipStream_t stream);
+hipError_t launch_role_n16_tile16(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
+hipError_t launch_role_tile32_64(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
 // RuleAgent community run (R = 0): rule_episode_kernel; hp_on [A] hysteresis state in/out
 hipError_t launch_rule_episode(const EpisodeParams& p, float* hp_on, hipStream_t stream);
 // shared table, N = 16, R <= 1 (configs[2]): episode_sq16_kernel; records packed like the fast path

@@ -9,7 +9,7 @@
 namespace p2pmg {
 namespace {
 
-// divisors the fast kernel divides by with the range-free quotient (fdiv_b in p2pmg_kernels.hip)
+// divisors the fast kernel divides by with the range-free quotient (fdiv_b in p2pmg_fastmath.h)
 bool host_div_range(float b) {
   const float m = std::fabs(b);
   return m >= 0x1p-40f && m <= 0x1p40f;

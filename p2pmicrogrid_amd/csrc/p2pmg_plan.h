@@ -13,7 +13,7 @@ struct PlanFacts {
   int S = 0, N = 0, R = 0, T = 0, A = 0;
   int n_cu = 256;  // compute units of the device (multiProcessorCount)
   int n_env = 0;
-  bool mi_ok = false;        // every max_in inside the fast division range (fdiv in p2pmg_kernels.hip)
+  bool mi_ok = false;        // every max_in inside the fast division range (fdiv in p2pmg_fastmath.h)
   bool battery = false;
   bool roles = false;        // cfg.shared_q == P2PMG_SHARED_ROLE
   bool thermal_set = false;  // p2pmg_set_thermal uploaded values (false: the config's, where sq16 applies)

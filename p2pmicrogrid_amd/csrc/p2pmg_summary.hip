@@ -20,7 +20,7 @@
 namespace p2pmg {
 namespace {
 
-// One packed record row of episode_fast_kernel / episode_sq16_kernel (FastRec in p2pmg_kernels.hip)
+// One packed record row of episode_fast_kernel / episode_sq16_kernel (FastRec in p2pmg_fastmath.h)
 struct PackedRow {
   float reward, cost, grid, p2p, tin;
   uint32_t actions;  // byte r: action of round r

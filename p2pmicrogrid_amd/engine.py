@@ -3,7 +3,7 @@
 This is the batched entry point the reference lacks (SURVEY.md §8b "Add a batched entry
 point over S scenarios"): one ``run_episode`` call is one ``CommunityMicrogrid.train_episode``
 (community.py:149-182) or ``run`` (community.py:95-123) for every scenario at once, executed
-by ONE HIP kernel launch (p2pmg_kernels.hip::episode_kernel).  The reference-shaped object API
+by ONE HIP kernel launch (p2pmg_general.hip::episode_kernel).  The reference-shaped object API
 (``community.CommunityMicrogrid`` & co.) is a thin layer over this class with S = 1.
 """
 from __future__ import annotations

@@ -3,7 +3,7 @@
 Here a battery is a parameter holder.  Its state of charge evolves on the device: the battery
 rule of the reference (RuleAgent._update_storage, agent.py:138-153, with BatteryStorage's
 sqrt(efficiency) bookkeeping, storage.py:36-76) runs inside the episode kernels
-(``battery_rule_r`` in p2pmg_kernels.hip) for communities whose agents carry a battery, and on
+(``battery_rule_r`` in p2pmg_fastmath.h) for communities whose agents carry a battery, and on
 explicit balance sequences through ``p2pmg_battery_seq`` (``BatteryStorage.apply_rule``).
 ``CommunityMicrogrid`` uploads capacities and SoC with ``p2pmg_set_battery`` before a launch and
 reads the SoC back with ``p2pmg_get_soc`` after it, as it does for the temperatures.

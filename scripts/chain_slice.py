@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Critical-chain listing of one step of episode_fast_kernel (configs[1]) from its ISA.
 
-    hipcc ... -gline-tables-only --cuda-device-only -S -DP2PMG_PART=1 ... -o fast.s
+    hipcc ... -gline-tables-only --cuda-device-only -S -DP2PMG_FAST_SLICE=0 ... p2pmicrogrid_amd/csrc/p2pmg_fast.hip -o fast.s
     python scripts/chain_slice.py fast.s <kernel-symbol-substring> > profiles/r03_fast/chain_listing.txt
 
 Takes the first unrolled step of the episode loop: from the step's first wait on the rows

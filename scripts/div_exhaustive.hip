@@ -1,4 +1,4 @@
-// Exhaustive check of the range-free f32 division forms of p2pmg_kernels.hip against the IEEE
+// Exhaustive check of the range-free f32 division forms of p2pmg_fastmath.h against the IEEE
 // quotient, over EVERY pair of 24-bit significands (2^23 x 2^23 = 7.0e13 pairs).
 //
 // The kernels divide a / b with a hoisted reciprocal y = fma(fma(-b, y0, 1), y0, y0), y0 =

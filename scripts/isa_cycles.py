@@ -2,7 +2,7 @@
 """Cycle-weighted VALU accounting of a kernel loop (static ISA x measured per-instruction costs).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize --cuda-device-only -S \\
-          -DP2PMG_PART=5 -I include -I p2pmicrogrid_amd/csrc p2pmicrogrid_amd/csrc/p2pmg_kernels.hip -o sq16.s
+          -I include -I p2pmicrogrid_amd/csrc p2pmicrogrid_amd/csrc/p2pmg_sq16.hip -o sq16.s
     python scripts/isa_cycles.py sq16.s <symbol-substring> <weights.json> > out.json
 
 Every VALU instruction of the loop (from the weights file's loop header to its back-edge block) is

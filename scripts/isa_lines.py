@@ -2,8 +2,8 @@
 """Per-source-line VALU accounting of one kernel's loop at HEAD (static ISA, -gline-tables-only).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -gline-tables-only \
-          --cuda-device-only -S -DP2PMG_PART=5 -I include -I p2pmicrogrid_amd/csrc \
-          p2pmicrogrid_amd/csrc/p2pmg_kernels.hip -o sq16.s
+          --cuda-device-only -S -I include -I p2pmicrogrid_amd/csrc \
+          p2pmicrogrid_amd/csrc/p2pmg_sq16.hip -o sq16.s
     python scripts/isa_lines.py sq16.s <symbol-substring> <weights.json> [phase-map.json]
 
 weights.json: {"loop": [first-block, last-block], "weights": {block: weight, ...}} -- every basic

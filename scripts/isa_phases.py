@@ -2,7 +2,7 @@
 """Per-phase instruction accounting of one kernel's ISA (static, from -gline-tables-only asm).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -gline-tables-only --cuda-device-only \
-          -S -DP2PMG_PART=5 -I include -I p2pmicrogrid_amd/csrc p2pmicrogrid_amd/csrc/p2pmg_kernels.hip -o sq16.s
+          -S -I include -I p2pmicrogrid_amd/csrc p2pmicrogrid_amd/csrc/p2pmg_sq16.hip -o sq16.s
     python scripts/isa_phases.py sq16.s <symbol-substring> <phase-map.json>
 
 Every instruction is attributed to the source line of the nearest preceding ``.loc``; a phase map

@@ -6,7 +6,7 @@ The bench workload (BASELINE configs[1]: thesis community N = 2, R = 1, T = 96, 
 tables, Philox exploration, the reference's epsilon schedule, T0 reset every episode) is run by
 oracle/restatement.py on a sample of its scenarios (every scenario is independent, so per-agent
 statistics do not depend on the batch).  For every agent-step the rows the fast kernel gathers are
-reconstructed (p2pmg_kernels.hip episode_fast_kernel, N = 2 candidate path):
+reconstructed (p2pmg_fast.hip episode_fast_kernel, N = 2 candidate path):
   * the round-0 row (strip + ip 10) when round 0 is greedy (exploring lanes skip it);
   * the three round-1 candidates, strip + ip(partner's round-0 action a'), a' = 0, 1, 2;
   * the next-state row (next time / balance bins, the same temperature bin, ip 10).

@@ -164,7 +164,7 @@ def test_device_count_without_gpu_is_zero_or_more():
 
 
 def test_battery_rule_rewrites_are_bitwise_identities():
-    """The kernels' range-free battery rule (p2pmg_kernels.hip battery_rule_pre / battery_rule_r) uses
+    """The kernels' range-free battery rule (p2pmg_fastmath.h battery_rule_pre / battery_rule_r) uses
     two rewrites of the reference arithmetic (agent.py:138-153, storage.py:52-76; oracle
     battery_rule): energy (b * 60) * 15 as b * 900 for an f32 balance b, and x - q as x + (-q).
     Both are exact identities in IEEE f64; checked here over random, extreme and signed-zero f32

@@ -1,7 +1,7 @@
 """Device fuzz of the kernels' fast division sequences against the IEEE operator, bit for bit.
 
 The episode kernels divide through a hoisted / per-round reciprocal and two Newton steps
-(p2pmg_kernels.hip fdiv_core, fdiv_core_pk, fdiv64, qcore64), relying on the argument that inside
+(p2pmg_fastmath.h fdiv_core, fdiv_core_pk, fdiv64, qcore64), relying on the argument that inside
 their guarded domains these ARE the IEEE quotient.  The reference's divisions they replace:
 agent.py:175 (balance / max_in), :193 (out * |f| / total), :203 (p2p / max_in), community.py:63
 (/ 60), heating.py:120 (/ margin) and storage.py:58,61,64 (/ capacity, / sqrt(eff), / 900).
