@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary) */
+#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag) */
 
 typedef struct p2pmg_ctx p2pmg_ctx;
 
@@ -431,6 +431,21 @@ int p2pmg_dqn_set_exchange(p2pmg_ctx* ctx, p2pmg_exchange_fn fn, void* user, int
 /* the shared-network gradient layout in use: segments of this context, agents per train
  * workgroup, train workgroups per env step */
 int p2pmg_dqn_grad_layout(p2pmg_ctx* ctx, int* segments, int* agents_per_block, int* blocks);
+
+/* Interleaved chains.  A chained launch (p2pmg_run_episodes) of the fast kernel may run TWO of an
+ * agent's consecutive episodes per 64-lane wave, episode e in lanes 0-31 and e + 1 in lanes 32-63,
+ * T / 2 steps behind (p2pmg_last_kernel: "...,interleaved>"), where the results stay those of the
+ * episodes run one after the other, bit for bit: Philox training with P2PMG_FLAG_RESET_T0 (the later
+ * episode starts from its own T0 draw), N = 2, no battery, T % 6 == 0, n_temp_states <= 32, and
+ * inputs whose hazard distance D allows it.  D is the largest u - v over an agent's steps u (of the
+ * earlier episode) and v (of the later) that touch Q rows of one (time bin, balance bin) key with a
+ * write involved; the launch interleaves iff D + 4 <= T / 2.  D depends only on what
+ * p2pmg_set_env / set_profiles / set_agent_params uploaded and is computed on the device by the first
+ * chained launch after an upload (T <= 512; beyond that D = -1 and the chain runs serially).
+ * P2PMG_INTERLEAVE=0 in the environment (read once per process) turns the form off.
+ * distance, safe (D + 4 <= T / 2): either may be NULL.  P2PMG_E_STATE before the first chained launch
+ * after an upload. */
+int p2pmg_chain_lag(p2pmg_ctx* ctx, int* distance, int* safe);
 
 #ifdef __cplusplus
 }

@@ -41,7 +41,7 @@ EXPORTS = [
     "p2pmg_dqn_set_buffer", "p2pmg_dqn_forward", "p2pmg_dqn_train_batch", "p2pmg_prepass_stats",
     "p2pmg_dqn_get_net_steps", "p2pmg_fdiv_check", "p2pmg_fdiv64_check", "p2pmg_comm_nranks",
     "p2pmg_allreduce_metrics", "p2pmg_table_hash_allgather", "p2pmg_dqn_set_exchange", "p2pmg_dqn_grad_layout",
-    "p2pmg_run_episodes", "p2pmg_get_episode_rewards",
+    "p2pmg_run_episodes", "p2pmg_get_episode_rewards", "p2pmg_chain_lag",
     "p2pmg_set_thermal", "p2pmg_get_thermal", "p2pmg_rc_step_ex", "p2pmg_get_hp_levels",
     "p2pmg_episode_summary",
 ]
@@ -162,6 +162,7 @@ def _declare(lib):
         "p2pmg_dqn_forward": ([vp, i32, i32, vp, vp], i32),
         "p2pmg_dqn_train_batch": ([vp, i32, vp, vp], i32),
         "p2pmg_prepass_stats": ([vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], i32),
+        "p2pmg_chain_lag": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int)], i32),
         "p2pmg_dqn_get_net_steps": ([vp, i32, i32, vp], i32),
         "p2pmg_fdiv_check": ([vp, i32, vp, vp, vp], i32),
         "p2pmg_fdiv64_check": ([vp, i32, vp, vp, vp], i32),

@@ -49,7 +49,19 @@ __device__ __forceinline__ void gather_even(float ev, float (&col)[N], int i) {
 #define P2PMG_BAT_SPEC 1  // configs[3] 59.6 -> 58.7 ms (profiles/r04_battery_ab.txt)
 #endif
 // BAT: 0 none, 1 battery with per-lane range tests, 2 battery in the launcher-verified domain
-template <int N, typename QT, int R1, bool TRAIN, int BAT, bool NARROW>
+// PIPE (chained training launches, no battery; the plan's `interleave`): two chained episodes per wave.
+// Lanes 0-31 run episodes 0, 2, 4, ... of their agents and lanes 32-63 episodes 1, 3, 5, ... of the SAME
+// agents, in lockstep, half an episode (L = T / 2 steps) behind: an agent's consecutive episodes are
+// coupled only through its table (the later one starts from its own T0 draw), and the launcher sends
+// this form only inputs whose hazard distance keeps every conflicting pair of row accesses at least
+// four steps apart in the order of the serial chain (chain_lag_kernel).  Lockstep time runs in phases
+// of L steps; at a phase boundary one half is at an episode boundary and runs the epilogue and the
+// prologue under a divergent branch.  What was wave-uniform per episode (step offsets, code-word
+// base) is per lane.  The one access whose serial order cannot be kept, step T - 1's next-state
+// row (key of step 0, which the follower episode has been writing since its own step 0), is served
+// from a snapshot of max3 of those rows that the follower takes in its prologue (LDS, one slot per
+// half, read by the other half L steps later).
+template <int N, typename QT, int R1, bool TRAIN, int BAT, bool NARROW, bool PIPE = false>
 __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams p, const uint2* __restrict__ pre,
                                                              FastRec* __restrict__ recs, int spw, int n_cons,
                                                              const PrepOut nxt) {
@@ -66,13 +78,16 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
   }
   constexpr int G = pow2ceil(N);
   static_assert(G <= 8 && R1 >= 1 && R1 <= 4, "fast path: G <= 8, R + 1 <= 4");
+  static_assert(!PIPE || (TRAIN && BAT == 0), "two episodes per wave: chained training launches without a battery");
   // N = 2: round 1's Q row is one of three (by the partner's round-0 action) whose bins the
   // pre-pass wrote; all three are issued a step ahead, so round 1 waits for no gather
   // (not with a battery: the partner's round-0 power then depends on its state of charge)
   constexpr bool CAND = N == 2 && R1 >= 2 && BAT == 0;
   const int lane = (int)threadIdx.x;
-  const int sl = lane / G;
-  const int i = lane % G;
+  const int grp = PIPE ? lane >> 5 : 0;    // PIPE: the half of the wave (even / odd episodes of the chain)
+  const int hl = PIPE ? (lane & 31) : lane;  // ... and the lane inside it: every exchange stays inside a half
+  const int sl = hl / G;
+  const int i = hl % G;
   const int s = (int)blockIdx.x * spw + sl;
   const bool active = i < N && sl < spw && s < p.S;
   const int a = active ? s * N + i : 0;
@@ -146,9 +161,59 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
   // them, and each wave starts its next episode as soon as its own ends): T_in / T_m carry over
   // in registers (with the end-of-episode T0 reset when requested), the Q rows through memory.
   const int n_chain = p.chain > 1 ? p.chain : 1;
-  for (int ep = 0; ep < n_chain; ++ep) {
-    const uint32_t* codes_a = p.codes + (size_t)ep * p.codes_stride + a;
-    char* rec_ptr = rec_on ? reinterpret_cast<char*>(recs) + (size_t)a * rec_bytes : rec_dummy;
+  // The state of the episode a lane runs: set by begin_episode, advanced by step.  PIPE: the two
+  // halves of the wave are L steps apart, so all of it is per lane there.
+  bool st_on = active;           // the lane stores (PIPE: and its half has an episode running)
+  size_t rec_adv = rec_step;     // record pointer advance per step
+  bool wrap_l = false;           // PIPE: this lane's step T - 1 takes max3 of the next-state row from the snapshot
+  bool wrap_it = false;          // PIPE: the loop's last iteration of a phase (uniform)
+  QT* snap = nullptr;            // PIPE: [2][32 temperature bins][32 lanes] max3 of the rows (key of step 0, bin, p2p = 0)
+  if constexpr (PIPE) {
+    __shared__ QT snap_lds[2 * 32 * 32];
+    snap = snap_lds;
+  }
+  const uint32_t* codes_a;
+  char* rec_ptr;
+  uint32_t TA, env_st, env_end, o3, eo3;
+  EnvV eS[3];
+  uint2 pS[3];
+  uint32_t cS[3];
+  uint32_t cw, strip, a0, aN;
+  int iT;
+  Row4<QT> row0, rowN;
+  uint32_t iS[3] = {0u, 0u, 0u};
+  Row4<QT> cand[3];
+  Patch<QT> pat{0xFFFFFFFFu, 0, (QT)0};
+  float ep_sum = 0.0f;
+  float t0_in = tin, t0_m = tm;
+  // masked-off lanes may explore too: they read agent 0's rows and store only to the dummy slots
+  auto code_of = [&](uint32_t w) { return TRAIN ? w : 0xFFFFFFFFu; };
+  // row arithmetic in 24-bit multiplies (full-rate v_mul_u32_u24; every operand < 2^24)
+  auto strip_of = [&](uint32_t base, int it_) { return __umul24(base + __umul24((uint32_t)it_, (uint32_t)nbv), (uint32_t)np); };
+  auto row0_addr = [&](uint32_t st, uint32_t nr, uint32_t c) -> uint32_t {
+    const bool need = ((c & 0xFF) == 255) || (TRAIN && R1 == 1);  // greedy, or the TD target itself
+    return need ? st + (uint32_t)ip_zero : nr;
+  };
+#if P2PMG_TRACE  // timing-only probe: per-step s_memtime splits of one wave, printed at the end
+  uint64_t trW = 0, trC = 0, trR = 0, trLast = 0, trA0 = 0, trWC = 0, trA1 = 0, trMid = 0, trCal = 0;
+#define P2PMG_STAMP(v) asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(v)::"memory")
+#endif
+  // An episode's prologue (ep: its index in the chain): ring fill, first rows, the T0 draw.  PIPE: runs
+  // under the divergent branch of a phase boundary, for one half of the wave.
+  auto begin_episode = [&](int ep) __attribute__((always_inline)) {
+    if constexpr (PIPE) {
+      if (ep >= 1 && st_on) {  // the reset at the end of episode ep - 1: drawn in this half's previous prologue
+        tin = t0_in;
+        tm = t0_m;
+      }
+    }
+    codes_a = p.codes + (size_t)(PIPE && ep < 0 ? 0 : ep) * p.codes_stride + a;
+    if constexpr (PIPE) {
+      rec_ptr = rec_on && st_on ? reinterpret_cast<char*>(recs) + (size_t)a * rec_bytes : rec_dummy;
+      rec_adv = st_on ? rec_step : 0;
+    } else {
+      rec_ptr = rec_on ? reinterpret_cast<char*>(recs) + (size_t)a * rec_bytes : rec_dummy;
+    }
     // The per-step inputs (env row, pre-pass word, code word, round-1 bins) are fresh HBM lines every
     // step, loaded three steps ahead into a 3-slot ring: slot t % 3 holds step t's, and step t
     // refills its own slot with step t + 3's once those are dead.  The step loop is unrolled by three,
@@ -156,31 +221,21 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
     // loads), and the refills are issued after the step's row gathers: loads complete in issue order,
     // so a stream load issued ahead of the gathers would hold up the wait for them.
     // Running (uniform, 32-bit) offsets of step t + 3, wrapping at T: T * A < 2^32 on this path.
-    const uint32_t TA = (uint32_t)T * (uint32_t)A, env_st = (uint32_t)env_step, env_end = env_st * (uint32_t)T;
-    uint32_t o3 = (uint32_t)(3 % T) * (uint32_t)A, eo3 = (uint32_t)(3 % T) * env_st;
+    TA = (uint32_t)T * (uint32_t)A, env_st = (uint32_t)env_step, env_end = env_st * (uint32_t)T;
+    o3 = (uint32_t)(3 % T) * (uint32_t)A, eo3 = (uint32_t)(3 % T) * env_st;
 
     // ring slots as vector values, so each stays one register tuple (a 16-B load's destination)
-    EnvV eS[3] = {load_envv(envb), load_envv(envb + (size_t)t1 * env_step), load_envv(envb + (size_t)t2 * env_step)};
-    uint2 pS[3] = {preb[0], preb[(size_t)t1 * A], preb[(size_t)t2 * A]};
-    uint32_t cS[3] = {codes_a[0], codes_a[(size_t)t1 * A], codes_a[(size_t)t2 * A]};
-    // masked-off lanes may explore too: they read agent 0's rows and store only to the dummy slots
-    auto code_of = [&](uint32_t w) { return TRAIN ? w : 0xFFFFFFFFu; };
-    uint32_t cw = code_of(cS[0]);
-    int iT = temp_bin(tin);
-    // row arithmetic in 24-bit multiplies (full-rate v_mul_u32_u24; every operand < 2^24)
-    auto strip_of = [&](uint32_t base, int it_) { return __umul24(base + __umul24((uint32_t)it_, (uint32_t)nbv), (uint32_t)np); };
-    uint32_t strip = strip_of(pS[0].y & 0xFFFFu, iT);
-    uint32_t nrow = strip_of(pS[0].y >> 16, iT) + (uint32_t)ip_zero;
-    auto row0_addr = [&](uint32_t st, uint32_t nr, uint32_t c) -> uint32_t {
-      const bool need = ((c & 0xFF) == 255) || (TRAIN && R1 == 1);  // greedy, or the TD target itself
-      return need ? st + (uint32_t)ip_zero : nr;
-    };
-    uint32_t a0 = row0_addr(strip, nrow, cw);
-    uint32_t aN = TRAIN ? nrow : a0;
-    Row4<QT> row0 = gat(a0);
-    Row4<QT> rowN = gat(aN);
-    uint32_t iS[3] = {0u, 0u, 0u};
-    Row4<QT> cand[3];
+    eS[0] = load_envv(envb), eS[1] = load_envv(envb + (size_t)t1 * env_step), eS[2] = load_envv(envb + (size_t)t2 * env_step);
+    pS[0] = preb[0], pS[1] = preb[(size_t)t1 * A], pS[2] = preb[(size_t)t2 * A];
+    cS[0] = codes_a[0], cS[1] = codes_a[(size_t)t1 * A], cS[2] = codes_a[(size_t)t2 * A];
+    cw = code_of(cS[0]);
+    iT = temp_bin(tin);
+    strip = strip_of(pS[0].y & 0xFFFFu, iT);
+    const uint32_t nrow = strip_of(pS[0].y >> 16, iT) + (uint32_t)ip_zero;
+    a0 = row0_addr(strip, nrow, cw);
+    aN = TRAIN ? nrow : a0;
+    row0 = gat(a0);
+    rowN = gat(aN);
     if constexpr (CAND) {
       iS[0] = ipc_a[0];
       iS[1] = ipc_a[(size_t)t1 * A];
@@ -188,377 +243,47 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
 #pragma unroll
       for (int b = 0; b < 3; ++b) cand[b] = gat((strip + ((iS[0] >> (8 * b)) & 0xFFu)));
     }
-    Patch<QT> pat{0xFFFFFFFFu, 0, (QT)0};
-    float ep_sum = 0.0f;
-    // the end-of-episode T0 reset depends only on (seed, episode + 1, agent): drawn here, while the
-    // first rows are in flight, and applied at the end (the f64 transcendentals off the episode tail)
-    float t0_in = tin, t0_m = tm;
-    if (p.reset_t0 && active)
-      t0_draw(p.seed_lo, p.seed_hi, p.episode + ep + 1, p.agent_offset + (uint32_t)a, k.setpoint, p.reset_sigma, t0_in,
-              t0_m);
-#if P2PMG_TRACE  // timing-only probe: per-step s_memtime splits of one wave, printed at the end
-    uint64_t trW = 0, trC = 0, trR = 0, trLast = 0, trA0 = 0, trWC = 0, trA1 = 0, trMid = 0, trCal = 0;
-#define P2PMG_STAMP(v) asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(v)::"memory")
-#endif
-    __builtin_amdgcn_s_waitcnt(0);  // enter the loop with nothing in flight (static waits inside)
-
-    // one step; the loop below runs it three times per iteration (a manual unroll: the DPP exchanges
-    // are convergent, so the compiler will not unroll a loop with a runtime trip count): the input
-    // ring's slots and the prefetched rows' alternating registers stay put
-    auto step = [&](auto par) __attribute__((always_inline)) {
-      constexpr int P = decltype(par)::value, P1 = (P + 1) % 3;  // slots of step t and of step t + 1
-      const EnvV ev = eS[P];
-      const EnvRow e0{0.0f, ev.x, ev.y, ev.z, ev.w};
-      const uint2 p0 = pS[P], p1 = pS[P1];
-      const uint32_t c1 = cS[P1], ipc0 = iS[P], ipc1 = iS[P1];
-      const float balw = __uint_as_float(p0.x);
-      float row[N];
-      float col[N];
+    pat = Patch<QT>{0xFFFFFFFFu, 0, (QT)0};
+    ep_sum = 0.0f;
+    if constexpr (!PIPE) {
+      // the end-of-episode T0 reset depends only on (seed, episode + 1, agent): drawn here, while the
+      // first rows are in flight, and applied at the end (the f64 transcendentals off the episode tail)
+      t0_in = tin, t0_m = tm;
+      if (p.reset_t0 && active)
+        t0_draw(p.seed_lo, p.seed_hi, p.episode + ep + 1, p.agent_offset + (uint32_t)a, k.setpoint, p.reset_sigma, t0_in,
+                t0_m);
+    } else {
+      // The snapshot for the other half's step T - 1: max3 of this agent's rows (key of step 0, every
+      // temperature bin, p2p = 0) as they are before this episode's first TD store.  The other half's
+      // stores to that key are at least four steps past (the hazard rule), so these are the values
+      // its serial step T - 1 would read.  Loaded kSnap rows at a time, the first batch under the T0 draw.
+      constexpr int kSnap = 10;
+      const uint32_t key0 = pS[0].y & 0xFFFFu;
+      const int nTi = p.nT;
+      Row4<QT> sr[kSnap];
+      auto snap_load = [&](int it0) {
 #pragma unroll
-      for (int j = 0; j < N; ++j) { row[j] = 0.0f; col[j] = 0.0f; }
-      // the next step's T_in, temperature bin and table strips for each of the 3 actions
-      // (heating.py:37-56, rl.py:93): they need only this step's state, so they run while the rows
-      // are in flight, and the final action then merely selects one set (issue_next)
-      float tinA[3];
-      uint32_t iTA[3], stA[3], nrA[3];
-      {
-        const float ain = k.inv_ri * (tm - tin) + k.inv_rvent * (e0.t_out - tin);
-#pragma unroll
-        for (int x = 0; x < 3; ++x) {
-          const float d_in = k.inv_ci * (ain + hin[x]);
-          tinA[x] = tin + (d_in * k.spm) * k.slot;
-          iTA[x] = (uint32_t)temp_bin(tinA[x]);
-          stA[x] = strip_of(p1.y & 0xFFFFu, (int)iTA[x]);
-          nrA[x] = strip_of(p1.y >> 16, (int)iTA[x]) + (uint32_t)ip_zero;
-        }
-      }
-      // Between the rows' arrival and the next step's gathers the wave issues on the critical path
-      // (the gathers' latency is the rest of the step): only what those addresses need goes there;
-      // the TD target row's patch, T_m, the records and the market wait until the gathers are out.
-      const Patch<QT> pprev = pat;    // the previous step's TD store
-#if P2PMG_TRACE
-      uint64_t tr0, tr1;
-      P2PMG_STAMP(tr0);
-      if (trLast) trR += tr0 - trLast;
-      asm volatile("" ::"v"(row0.v[0]), "v"(row0.v[1]), "v"(row0.v[2]));
-      P2PMG_STAMP(tr1);
-      trW += tr1 - tr0;
-      {  // calibration: the cost of one stamp (two back to back)
-        uint64_t tcal;
-        P2PMG_STAMP(tcal);
-        trCal += tcal - tr1;
-        tr1 = tcal;
-      }
-      trMid = tr1;  // no candidate rows (N != 2 or a battery): "round1" runs from the rows' arrival
-#endif
-      double soc_r = soc;  // tentative SoC of the current round
-      BatPre bpre{};
-      if constexpr (BAT == 2) bpre = bat_pre(soc, bcap, bk);  // shared by the step's rounds
-      auto bat_rule = [&](float o, double& sr) -> float {
-        if constexpr (BAT == 2) return (float)battery_rule_pre((double)o, sr, rcap, bk, bpre);
-        return (float)battery_rule_r<true>((double)o, sr, bcap, rcap, bk);
+        for (int j = 0; j < kSnap; ++j) sr[j] = gat(strip_of(key0, it0 + j < nTi ? it0 + j : nTi - 1) + (uint32_t)ip_zero);
       };
-      // (round 0's rule for all 3 actions ahead of the rows' wait measured slower: configs[3] 57.1 ->
-      // 59.5 ms, profiles/r05_ab/bat_spec0_ab.txt)
-      row0 = patched(row0, a0, pat);  // ... may have hit a prefetched row
-
-      // round 0 (P = 0: every filtered power is -0, tot = 0, even split)
-      int code = (int)(cw & 0xFF);
-      int act = code == 255 ? argmax3(row0) : code;
-      float hp = hp_of(lv, act);
-      int ip = ip_zero;
-      Row4<QT> rowR = row0;
-      uint32_t acts = (uint32_t)act, ips = (uint32_t)ip_zero;
-      // CommunityMicrogrid._step -> HPHeating.step (community.py:184-188, heating.py:138-143) needs
-      // only the final round's heat-pump power: it and the next step's row gathers are issued as soon
-      // as that is known, ahead of the final round's divide-power and this step's market work
-      float tin1 = tin, tm1 = tm;
-      int iT1 = 0;
-      uint32_t strip1 = 0, cw1 = 0, a0n = 0, aNn = 0;
-      Row4<QT> row0n, rowNn, candn[3];
-      Sel3M mnext{};
-      auto issue_next = [&](int act_final) {
-        const Sel3M m = sel3_masks(act_final);
-        mnext = m;
-        strip1 = __float_as_uint(sel3(m, __uint_as_float(stA[0]), __uint_as_float(stA[1]), __uint_as_float(stA[2])));
-        const uint32_t nrow1 =
-            __float_as_uint(sel3(m, __uint_as_float(nrA[0]), __uint_as_float(nrA[1]), __uint_as_float(nrA[2])));
-        cw1 = code_of(c1);
-        a0n = row0_addr(strip1, nrow1, cw1);
-        aNn = TRAIN ? nrow1 : a0n;
-#if P2PMG_ABLATE == 8 || P2PMG_ABLATE == 10
-        row0n = fake_row(q + a0n * kQPad);
-        rowNn = fake_row(q + aNn * kQPad);
-#else
-        // the rows round 0 and round 1 wait for first, the TD's next-state row last.  Round 0's row
-        // only for the lanes that read it (a greedy round 0, or the TD target at R = 0): an exploring
-        // lane's gather would be address work in the CU's memory pipeline for nothing (an exec-masked
-        // load; configs[1] 79.8 -> 79.0 us, configs[3] 66.2 -> 65.3 ms at the bench's epsilon)
-        {
-          Row4<QT> r0{};
-          if (((cw1 & 0xFF) == 255) || (TRAIN && R1 == 1)) r0 = gat(a0n);
-          row0n = r0;
-        }
-#endif
-        if constexpr (CAND) {
+      auto snap_store = [&](int it0) {
 #pragma unroll
-          for (int b = 0; b < 3; ++b) candn[b] = gat((strip1 + ((ipc1 >> (8 * b)) & 0xFFu)));
-        }
-#if !(P2PMG_ABLATE == 8 || P2PMG_ABLATE == 10)
-        rowNn = gat(aNn);
-#endif
+        for (int j = 0; j < kSnap; ++j)
+          if (it0 + j < nTi) snap[(grp * 32 + it0 + j) * 32 + hl] = max3(sr[j]);
       };
-      // step t + 3's code word and round-1 bins into this step's slots (dead since step t - 1 / round 1)
-      auto refill_words = [&]() {
-        cS[P] = codes_a[o3];
-        if constexpr (CAND) iS[P] = ipc_a[o3];
-      };
-      // the rest of HPHeating.step for the chosen level, once the gathers are out
-      auto settle_next = [&]() {
-        const Sel3M& m = mnext;
-        iT1 = (int)__float_as_uint(sel3(m, __uint_as_float(iTA[0]), __uint_as_float(iTA[1]), __uint_as_float(iTA[2])));
-        tin1 = sel3(m, tinA[0], tinA[1], tinA[2]);
-        const float d_m = k.inv_cm * (((k.inv_ri * (tin - tm) + k.inv_re * (e0.t_out - tm)) + k.solar) +
-                                      sel3(m, hm[0], hm[1], hm[2]));  // heating.py:45,48
-        tm1 = tm + (d_m * k.spm) * k.slot;
-      };
-      if constexpr (R1 == 1) {
-        issue_next(act);
-        refill_words();
-        settle_next();
+      snap_load(0);
+      // the T0 this half's NEXT episode (ep + 2) starts from, or the one the chain leaves behind
+      if (active)
+        t0_draw(p.seed_lo, p.seed_hi, p.episode + (ep + 2 < n_chain ? ep + 2 : n_chain), p.agent_offset + (uint32_t)a,
+                k.setpoint, p.reset_sigma, t0_in, t0_m);
+      snap_store(0);
+      for (int it0 = kSnap; it0 < nTi; it0 += kSnap) {
+        snap_load(it0);
+        snap_store(it0);
       }
-      float out0 = balw + hp;
-      if constexpr (BAT != 0) {
-        if (bcap > 0.0) out0 = bat_rule(out0, soc_r);
-      }
-      const float ev0 = div_n_r<N>(out0 * 1.0f, rn);
-#pragma unroll
-      for (int j = 0; j < N; ++j) row[j] = ev0;
-#pragma unroll
-      for (int r = 1; r < R1; ++r) {
-        if (r == 1) {
-          gather_even<N, 1, G>(ev0, col, i);
-        } else {
-          exchange<N>(row, col, i, sl, nullptr);
-        }
-        code = (int)((cw >> (8 * r)) & 0xFF);
-        if (CAND && r == 1) {
-          // the partner's round-0 action picks the prefetched row (its bin is byte b of ipc0)
-          const int b = __float_as_int(shfl_xor_c<1>(__int_as_float(act)));
-#if P2PMG_TRACE
-          {
-            uint64_t ta, tb;
-            asm volatile("" ::"v"(b));
-            P2PMG_STAMP(ta);
-            asm volatile("" ::"v"(cand[0].v[0]), "v"(cand[1].v[0]), "v"(cand[2].v[0]), "v"(cand[0].v[2]), "v"(cand[1].v[2]),
-                         "v"(cand[2].v[2]));
-            P2PMG_STAMP(tb);
-            trA0 += ta - tr1;
-            trWC += tb - ta;
-            trMid = tb;
-          }
-#endif
-          ip = (int)((ipc0 >> (8 * b)) & 0xFFu);
-          rowR = patched(sel_row(b, cand[0], cand[1], cand[2]), strip + (uint32_t)ip, pat);
-        } else {
-          float acc = 0.0f;
-#pragma unroll
-          for (int j = 0; j < N; ++j) acc = acc + (-((j == i) ? 0.0f : col[j]));
-          ip = p2p_bin(fdiv_b(div_n_r<N>(acc, rn), rmi));
-          const bool need = code == 255 || (TRAIN && r == R1 - 1);
-#if P2PMG_ABLATE == 7
-          rowR = fake_row(q + (need ? strip + (uint32_t)ip : a0) * kQPad);
-#else
-          rowR = gat((need ? strip + (uint32_t)ip : a0));
-#endif
-        }
-#if P2PMG_BAT_SPEC
-        // the final round's battery rule for each of the 3 actions while its row is in flight (it
-        // needs only balw, the level and this step's SoC): the action then only selects
-        float outA[3];
-        double socA[3];
-        if constexpr (BAT != 0) {
-          if (r == R1 - 1) {
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-              socA[x] = soc;
-              outA[x] = balw + hp_of(lv, x);
-              if (bcap > 0.0) outA[x] = bat_rule(outA[x], socA[x]);
-            }
-          }
-        }
-#endif
-        act = code == 255 ? argmax3(rowR) : code;
-        acts |= (uint32_t)act << (8 * r);
-        ips |= (uint32_t)ip << (8 * r);
-        hp = hp_of(lv, act);
-        if (r == R1 - 1) {
-#if P2PMG_TRACE
-          {
-            uint64_t tc;
-            asm volatile("" ::"v"(act));
-            P2PMG_STAMP(tc);
-            trA1 += tc - trMid;
-            trMid = tc;
-          }
-#endif
-          issue_next(act);
-#if P2PMG_TRACE
-          P2PMG_STAMP(trLast);
-          trC += trLast - trMid;
-#endif
-          refill_words();
-          settle_next();
-        }
-        float out = balw + hp;
-        if constexpr (BAT != 0) {
-#if P2PMG_BAT_SPEC
-          if (r == R1 - 1) {
-            const Sel3M m = sel3_masks(act);
-            out = sel3(m, outA[0], outA[1], outA[2]);
-            soc_r = sel3(m, socA[0], socA[1], socA[2]);
-          } else
-#endif
-          {
-            soc_r = soc;
-            if (bcap > 0.0) out = bat_rule(out, soc_r);
-          }
-        }
-#if P2PMG_ABLATE == 11  // timing-only: no final-round divide-power and no market (cost from out alone)
-        if (r == R1 - 1) {
-          row[0] = out;
-          continue;
-        }
-#endif
-        // _divide_power's filter keeps pw where sign(out) != sign(pw) (agent.py:187-188): for out > 0
-        // that is pw <= 0, for out < 0 pw >= 0, for out = 0 any pw.  A kept pw = +-0 and a dropped
-        // one (0) are interchangeable: every later use is |f| or a sum that already holds +0.
-        // As one clamp: f = med3(pw, out < 0 ? 0 : -inf, out > 0 ? 0 : +inf).
-        const float flo = out < 0.0f ? 0.0f : -__builtin_inff(), fhi = out > 0.0f ? 0.0f : __builtin_inff();
-        float f[N];
-        float tot = 0.0f;
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-          const float pw = -((j == i) ? 0.0f : col[j]);
-          f[j] = __builtin_amdgcn_fmed3f(pw, flo, fhi);
-          tot = tot + f[j];
-        }
-        tot = fabsf(tot);
-        const float ev = div_n_r<N>(out * 1.0f, rn);
-        // out * |f_j| / tot for every j: the diagonal's f_ii = +-0 gives out * 0 / tot = out * 0, the
-        // reference's value for it (agent.py:193-194), for any tot > 0.  One range guard per round.
-        const Recip rt = recip(tot == 0.0f ? 1.0f : tot);  // the tot = 0 lanes take ev
-        const float nout = nabs_out(out);
-        float num[N];
-        bool bad = !rt.ok;
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-          num[j] = nout * f[j];
-          row[j] = fdiv_core(num[j], rt);
-          bad = bad || !fdiv_ok(num[j]);
-        }
-        if (bad) {
-#pragma unroll
-          for (int j = 0; j < N; ++j) row[j] = fdiv_ieee(num[j], rt.b);
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) row[j] = (tot == 0.0f) ? ev : row[j];
-      }
-      soc = soc_r;  // BatteryStorage state after the final round's decision
-      pat.row = 0xFFFFFFFFu;  // the next step's rows were issued after the previous TD store
-
-      // CommunityMicrogrid._assign_powers community.py:45-54 on the final P (diagonal kept)
-      float g = 0.0f, pp = 0.0f;
-#if P2PMG_ABLATE == 11
-      g = row[0];
-#else
-      exchange<N>(row, col, i, sl, nullptr);
-#pragma unroll
-      for (int j = 0; j < N; ++j) {
-        // ex = sign(pij) * min(|pij|, |pji|) where the signs differ (community.py:48-50)
-        const float pij = row[j], pji = col[j];
-        const float ex = pair_exchange(pij, pji);
-        g = g + (pij - ex);
-        pp = pp + ex;
-      }
-#endif
-      // CommunityMicrogrid._compute_costs community.py:56-65
-      float cost = (g >= 0.0f) ? g * e0.buy : g * e0.inj;
-      cost = cost + pp * e0.p2p;
-      cost = fdiv_b(cost * k.slot, rmph);
-      cost = cost * k.kilo;
-      // RLAgent.get_reward agent.py:225-232 (pre-update T_in)
-      float pen = fmaxf(fmaxf(0.0f, k.lower - tin), fmaxf(0.0f, tin - k.upper));
-      pen = pen > 0.0f ? pen + 1.0f : 0.0f;
-      const float rw = -(cost + k.penw * pen);
-
-      if constexpr (TRAIN) {
-        // QAgent.train agent.py:293-298 -> QActor.train rl.py:119-129
-        const uint32_t srow = strip + (uint32_t)ip;
-        const QT qsa = sel3(act, rowR.v[0], rowR.v[1], rowR.v[2]);
-        const QT qnew = td_update(qsa, rw, max3(patched(rowN, aN, pprev)), k.alpha, k.gamma);
-        *(active ? q + srow * kQPad + act : q_dummy) = qnew;
-#if P2PMG_ABLATE == 9 || P2PMG_ABLATE == 10
-        pat = Patch<QT>{0xFFFFFFFFu, 0, (QT)0};  // timing-only: the next step does not wait for this TD
-#else
-        pat = Patch<QT>{srow, act, qnew};  // rows issued before this store see the old value
-#endif
-      }
-      if constexpr (narrow) {
-        *reinterpret_cast<float2*>(__builtin_assume_aligned(rec_ptr, 8)) = make_float2(rw, cost);
-      } else {
-        const uint32_t bins = (p0.y & 0xFFFFu) | ((uint32_t)iT << 16);  // it * nT*nb + ib | iT << 16
-        float4* rp = reinterpret_cast<float4*>(__builtin_assume_aligned(rec_ptr, 16));
-        rp[0] = make_float4(rw, cost, g, pp);
-        rp[1] = make_float4(tin, __uint_as_float(acts), __uint_as_float(bins), __uint_as_float(ips));
-      }
-      rec_ptr += rec_step;
-      // step t's env row and pre-pass word are dead: step t + 3's into their slots (the barrier keeps
-      // the scheduler from hoisting the loads above the old values' last use, which would need a
-      // second register set and a copy at the loop's back edge)
-      asm volatile("" ::: "memory");
-      eS[P] = load_envv(envb + eo3);
-      pS[P] = preb[o3];
-      // avg_reward = sum_t mean_i r (community.py:179), canonical sequential order
-      const float m = group_sum<N>(rw, lane, i, sl, nullptr);
-      ep_sum = ep_sum + div_n_r<N>(m, rn);
-
-      tin = tin1;
-      tm = tm1;
-      iT = iT1;
-      o3 += (uint32_t)A;
-      o3 = o3 == TA ? 0u : o3;
-      eo3 += env_st;
-      eo3 = eo3 == env_end ? 0u : eo3;
-      strip = strip1;
-      cw = cw1;
-      a0 = a0n;
-      aN = aNn;
-      row0 = row0n;
-      rowN = rowNn;
-      if constexpr (CAND) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b) cand[b] = candn[b];
-      }
-    };
-    using S0 = std::integral_constant<int, 0>;
-    using S1 = std::integral_constant<int, 1>;
-    using S2 = std::integral_constant<int, 2>;
-    int t = 0;
-    for (; t + 3 <= T; t += 3) {
-      step(S0{});
-      step(S1{});
-      step(S2{});
     }
-    if (t < T) step(S0{});
-    if (t + 1 < T) step(S1{});
-#if P2PMG_TRACE
-    if (threadIdx.x == 0 && (blockIdx.x == 0 || (int)blockIdx.x == n_cons / 2 || (int)blockIdx.x == n_cons - 1))
-      printf("TRACE blk %d/%d T %d: per step wait %.1f round0 %.1f waitcand %.1f round1 %.1f issue %.1f rest %.1f "
-             "(one stamp %.1f)\n",
-             (int)blockIdx.x, n_cons, T, (double)trW / T, (double)trA0 / T, (double)trWC / T, (double)trA1 / T,
-             (double)trC / T, (double)trR / (T - 1), (double)trCal / T);
-#endif
+  };
+  // the end of an episode (non-PIPE)
+  auto end_episode = [&](int ep) __attribute__((always_inline)) {
     if (active) {
       if (p.reset_t0) {  // agent.reset() at the end of train_episode (community.py:181), fused
         tin = t0_in;
@@ -569,19 +294,446 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
         if (ep == n_chain - 1) p.ep_reward[s] = ep_sum;
       }
     }
-  }  // chain
-  if (active) {
-    p.t_in[a] = tin;
-    p.t_m[a] = tm;
-    if constexpr (BAT != 0) p.soc[a] = soc;
+  };
+
+  // one step; the loop below runs it three times per iteration (a manual unroll: the DPP exchanges
+  // are convergent, so the compiler will not unroll a loop with a runtime trip count): the input
+  // ring's slots and the prefetched rows' alternating registers stay put
+  auto step = [&](auto par) __attribute__((always_inline)) {
+    constexpr int P = decltype(par)::value, P1 = (P + 1) % 3;  // slots of step t and of step t + 1
+    const EnvV ev = eS[P];
+    const EnvRow e0{0.0f, ev.x, ev.y, ev.z, ev.w};
+    const uint2 p0 = pS[P], p1 = pS[P1];
+    const uint32_t c1 = cS[P1], ipc0 = iS[P], ipc1 = iS[P1];
+    const float balw = __uint_as_float(p0.x);
+    float row[N];
+    float col[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) { row[j] = 0.0f; col[j] = 0.0f; }
+    // the next step's T_in, temperature bin and table strips for each of the 3 actions
+    // (heating.py:37-56, rl.py:93): they need only this step's state, so they run while the rows
+    // are in flight, and the final action then merely selects one set (issue_next)
+    float tinA[3];
+    uint32_t iTA[3], stA[3], nrA[3];
+    {
+      const float ain = k.inv_ri * (tm - tin) + k.inv_rvent * (e0.t_out - tin);
+#pragma unroll
+      for (int x = 0; x < 3; ++x) {
+        const float d_in = k.inv_ci * (ain + hin[x]);
+        tinA[x] = tin + (d_in * k.spm) * k.slot;
+        iTA[x] = (uint32_t)temp_bin(tinA[x]);
+        stA[x] = strip_of(p1.y & 0xFFFFu, (int)iTA[x]);
+        nrA[x] = strip_of(p1.y >> 16, (int)iTA[x]) + (uint32_t)ip_zero;
+      }
+    }
+    // Between the rows' arrival and the next step's gathers the wave issues on the critical path
+    // (the gathers' latency is the rest of the step): only what those addresses need goes there;
+    // the TD target row's patch, T_m, the records and the market wait until the gathers are out.
+    const Patch<QT> pprev = pat;    // the previous step's TD store
+#if P2PMG_TRACE
+    uint64_t tr0, tr1;
+    P2PMG_STAMP(tr0);
+    if (trLast) trR += tr0 - trLast;
+    asm volatile("" ::"v"(row0.v[0]), "v"(row0.v[1]), "v"(row0.v[2]));
+    P2PMG_STAMP(tr1);
+    trW += tr1 - tr0;
+    {  // calibration: the cost of one stamp (two back to back)
+      uint64_t tcal;
+      P2PMG_STAMP(tcal);
+      trCal += tcal - tr1;
+      tr1 = tcal;
+    }
+    trMid = tr1;  // no candidate rows (N != 2 or a battery): "round1" runs from the rows' arrival
+#endif
+    double soc_r = soc;  // tentative SoC of the current round
+    BatPre bpre{};
+    if constexpr (BAT == 2) bpre = bat_pre(soc, bcap, bk);  // shared by the step's rounds
+    auto bat_rule = [&](float o, double& sr) -> float {
+      if constexpr (BAT == 2) return (float)battery_rule_pre((double)o, sr, rcap, bk, bpre);
+      return (float)battery_rule_r<true>((double)o, sr, bcap, rcap, bk);
+    };
+    // (round 0's rule for all 3 actions ahead of the rows' wait measured slower: configs[3] 57.1 ->
+    // 59.5 ms, profiles/r05_ab/bat_spec0_ab.txt)
+    row0 = patched(row0, a0, pat);  // ... may have hit a prefetched row
+
+    // round 0 (P = 0: every filtered power is -0, tot = 0, even split)
+    int code = (int)(cw & 0xFF);
+    int act = code == 255 ? argmax3(row0) : code;
+    float hp = hp_of(lv, act);
+    int ip = ip_zero;
+    Row4<QT> rowR = row0;
+    uint32_t acts = (uint32_t)act, ips = (uint32_t)ip_zero;
+    // CommunityMicrogrid._step -> HPHeating.step (community.py:184-188, heating.py:138-143) needs
+    // only the final round's heat-pump power: it and the next step's row gathers are issued as soon
+    // as that is known, ahead of the final round's divide-power and this step's market work
+    float tin1 = tin, tm1 = tm;
+    int iT1 = 0;
+    uint32_t strip1 = 0, cw1 = 0, a0n = 0, aNn = 0;
+    Row4<QT> row0n, rowNn, candn[3];
+    Sel3M mnext{};
+    auto issue_next = [&](int act_final) {
+      const Sel3M m = sel3_masks(act_final);
+      mnext = m;
+      strip1 = __float_as_uint(sel3(m, __uint_as_float(stA[0]), __uint_as_float(stA[1]), __uint_as_float(stA[2])));
+      const uint32_t nrow1 =
+          __float_as_uint(sel3(m, __uint_as_float(nrA[0]), __uint_as_float(nrA[1]), __uint_as_float(nrA[2])));
+      cw1 = code_of(c1);
+      a0n = row0_addr(strip1, nrow1, cw1);
+      aNn = TRAIN ? nrow1 : a0n;
+#if P2PMG_ABLATE == 8 || P2PMG_ABLATE == 10
+      row0n = fake_row(q + a0n * kQPad);
+      rowNn = fake_row(q + aNn * kQPad);
+#else
+      // the rows round 0 and round 1 wait for first, the TD's next-state row last.  Round 0's row
+      // only for the lanes that read it (a greedy round 0, or the TD target at R = 0): an exploring
+      // lane's gather would be address work in the CU's memory pipeline for nothing (an exec-masked
+      // load; configs[1] 79.8 -> 79.0 us, configs[3] 66.2 -> 65.3 ms at the bench's epsilon)
+      {
+        Row4<QT> r0{};
+        if (((cw1 & 0xFF) == 255) || (TRAIN && R1 == 1)) r0 = gat(a0n);
+        row0n = r0;
+      }
+#endif
+      if constexpr (CAND) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) candn[b] = gat((strip1 + ((ipc1 >> (8 * b)) & 0xFFu)));
+      }
+#if !(P2PMG_ABLATE == 8 || P2PMG_ABLATE == 10)
+      rowNn = gat(aNn);
+#endif
+    };
+    // step t + 3's code word and round-1 bins into this step's slots (dead since step t - 1 / round 1)
+    auto refill_words = [&]() {
+      cS[P] = codes_a[o3];
+      if constexpr (CAND) iS[P] = ipc_a[o3];
+    };
+    // the rest of HPHeating.step for the chosen level, once the gathers are out
+    auto settle_next = [&]() {
+      const Sel3M& m = mnext;
+      iT1 = (int)__float_as_uint(sel3(m, __uint_as_float(iTA[0]), __uint_as_float(iTA[1]), __uint_as_float(iTA[2])));
+      tin1 = sel3(m, tinA[0], tinA[1], tinA[2]);
+      const float d_m = k.inv_cm * (((k.inv_ri * (tin - tm) + k.inv_re * (e0.t_out - tm)) + k.solar) +
+                                    sel3(m, hm[0], hm[1], hm[2]));  // heating.py:45,48
+      tm1 = tm + (d_m * k.spm) * k.slot;
+    };
+    if constexpr (R1 == 1) {
+      issue_next(act);
+      refill_words();
+      settle_next();
+    }
+    float out0 = balw + hp;
+    if constexpr (BAT != 0) {
+      if (bcap > 0.0) out0 = bat_rule(out0, soc_r);
+    }
+    const float ev0 = div_n_r<N>(out0 * 1.0f, rn);
+#pragma unroll
+    for (int j = 0; j < N; ++j) row[j] = ev0;
+#pragma unroll
+    for (int r = 1; r < R1; ++r) {
+      if (r == 1) {
+        gather_even<N, 1, G>(ev0, col, i);
+      } else {
+        exchange<N>(row, col, i, sl, nullptr);
+      }
+      code = (int)((cw >> (8 * r)) & 0xFF);
+      if (CAND && r == 1) {
+        // the partner's round-0 action picks the prefetched row (its bin is byte b of ipc0)
+        const int b = __float_as_int(shfl_xor_c<1>(__int_as_float(act)));
+#if P2PMG_TRACE
+        {
+          uint64_t ta, tb;
+          asm volatile("" ::"v"(b));
+          P2PMG_STAMP(ta);
+          asm volatile("" ::"v"(cand[0].v[0]), "v"(cand[1].v[0]), "v"(cand[2].v[0]), "v"(cand[0].v[2]), "v"(cand[1].v[2]),
+                       "v"(cand[2].v[2]));
+          P2PMG_STAMP(tb);
+          trA0 += ta - tr1;
+          trWC += tb - ta;
+          trMid = tb;
+        }
+#endif
+        ip = (int)((ipc0 >> (8 * b)) & 0xFFu);
+        rowR = patched(sel_row(b, cand[0], cand[1], cand[2]), strip + (uint32_t)ip, pat);
+      } else {
+        float acc = 0.0f;
+#pragma unroll
+        for (int j = 0; j < N; ++j) acc = acc + (-((j == i) ? 0.0f : col[j]));
+        ip = p2p_bin(fdiv_b(div_n_r<N>(acc, rn), rmi));
+        const bool need = code == 255 || (TRAIN && r == R1 - 1);
+#if P2PMG_ABLATE == 7
+        rowR = fake_row(q + (need ? strip + (uint32_t)ip : a0) * kQPad);
+#else
+        rowR = gat((need ? strip + (uint32_t)ip : a0));
+#endif
+      }
+#if P2PMG_BAT_SPEC
+      // the final round's battery rule for each of the 3 actions while its row is in flight (it
+      // needs only balw, the level and this step's SoC): the action then only selects
+      float outA[3];
+      double socA[3];
+      if constexpr (BAT != 0) {
+        if (r == R1 - 1) {
+#pragma unroll
+          for (int x = 0; x < 3; ++x) {
+            socA[x] = soc;
+            outA[x] = balw + hp_of(lv, x);
+            if (bcap > 0.0) outA[x] = bat_rule(outA[x], socA[x]);
+          }
+        }
+      }
+#endif
+      act = code == 255 ? argmax3(rowR) : code;
+      acts |= (uint32_t)act << (8 * r);
+      ips |= (uint32_t)ip << (8 * r);
+      hp = hp_of(lv, act);
+      if (r == R1 - 1) {
+#if P2PMG_TRACE
+        {
+          uint64_t tc;
+          asm volatile("" ::"v"(act));
+          P2PMG_STAMP(tc);
+          trA1 += tc - trMid;
+          trMid = tc;
+        }
+#endif
+        issue_next(act);
+#if P2PMG_TRACE
+        P2PMG_STAMP(trLast);
+        trC += trLast - trMid;
+#endif
+        refill_words();
+        settle_next();
+      }
+      float out = balw + hp;
+      if constexpr (BAT != 0) {
+#if P2PMG_BAT_SPEC
+        if (r == R1 - 1) {
+          const Sel3M m = sel3_masks(act);
+          out = sel3(m, outA[0], outA[1], outA[2]);
+          soc_r = sel3(m, socA[0], socA[1], socA[2]);
+        } else
+#endif
+        {
+          soc_r = soc;
+          if (bcap > 0.0) out = bat_rule(out, soc_r);
+        }
+      }
+#if P2PMG_ABLATE == 11  // timing-only: no final-round divide-power and no market (cost from out alone)
+      if (r == R1 - 1) {
+        row[0] = out;
+        continue;
+      }
+#endif
+      // _divide_power's filter keeps pw where sign(out) != sign(pw) (agent.py:187-188): for out > 0
+      // that is pw <= 0, for out < 0 pw >= 0, for out = 0 any pw.  A kept pw = +-0 and a dropped
+      // one (0) are interchangeable: every later use is |f| or a sum that already holds +0.
+      // As one clamp: f = med3(pw, out < 0 ? 0 : -inf, out > 0 ? 0 : +inf).
+      const float flo = out < 0.0f ? 0.0f : -__builtin_inff(), fhi = out > 0.0f ? 0.0f : __builtin_inff();
+      float f[N];
+      float tot = 0.0f;
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        const float pw = -((j == i) ? 0.0f : col[j]);
+        f[j] = __builtin_amdgcn_fmed3f(pw, flo, fhi);
+        tot = tot + f[j];
+      }
+      tot = fabsf(tot);
+      const float ev = div_n_r<N>(out * 1.0f, rn);
+      // out * |f_j| / tot for every j: the diagonal's f_ii = +-0 gives out * 0 / tot = out * 0, the
+      // reference's value for it (agent.py:193-194), for any tot > 0.  One range guard per round.
+      const Recip rt = recip(tot == 0.0f ? 1.0f : tot);  // the tot = 0 lanes take ev
+      const float nout = nabs_out(out);
+      float num[N];
+      bool bad = !rt.ok;
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        num[j] = nout * f[j];
+        row[j] = fdiv_core(num[j], rt);
+        bad = bad || !fdiv_ok(num[j]);
+      }
+      if (bad) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) row[j] = fdiv_ieee(num[j], rt.b);
+      }
+#pragma unroll
+      for (int j = 0; j < N; ++j) row[j] = (tot == 0.0f) ? ev : row[j];
+    }
+    soc = soc_r;  // BatteryStorage state after the final round's decision
+    pat.row = 0xFFFFFFFFu;  // the next step's rows were issued after the previous TD store
+
+    // CommunityMicrogrid._assign_powers community.py:45-54 on the final P (diagonal kept)
+    float g = 0.0f, pp = 0.0f;
+#if P2PMG_ABLATE == 11
+    g = row[0];
+#else
+    exchange<N>(row, col, i, sl, nullptr);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      // ex = sign(pij) * min(|pij|, |pji|) where the signs differ (community.py:48-50)
+      const float pij = row[j], pji = col[j];
+      const float ex = pair_exchange(pij, pji);
+      g = g + (pij - ex);
+      pp = pp + ex;
+    }
+#endif
+    // CommunityMicrogrid._compute_costs community.py:56-65
+    float cost = (g >= 0.0f) ? g * e0.buy : g * e0.inj;
+    cost = cost + pp * e0.p2p;
+    cost = fdiv_b(cost * k.slot, rmph);
+    cost = cost * k.kilo;
+    // RLAgent.get_reward agent.py:225-232 (pre-update T_in)
+    float pen = fmaxf(fmaxf(0.0f, k.lower - tin), fmaxf(0.0f, tin - k.upper));
+    pen = pen > 0.0f ? pen + 1.0f : 0.0f;
+    const float rw = -(cost + k.penw * pen);
+
+    if constexpr (TRAIN) {
+      // QAgent.train agent.py:293-298 -> QActor.train rl.py:119-129
+      const uint32_t srow = strip + (uint32_t)ip;
+      const QT qsa = sel3(act, rowR.v[0], rowR.v[1], rowR.v[2]);
+      QT qmax = max3(patched(rowN, aN, pprev));
+      if constexpr (PIPE && P == 2) {
+        // step T - 1 of an episode with a follower: its next-state row (key of step 0) has been
+        // written by the follower since its own step 0; the follower's snapshot holds what the
+        // serial chain reads here (the row's load above is still issued: the waits stay static)
+        if (wrap_it) {
+          const QT sv = snap[((grp ^ 1) * 32 + iT) * 32 + hl];
+#if P2PMG_ABLATE != 12  // 12 (test-only): the loaded row, which the follower has overwritten; the dense-collision test must then fail
+          qmax = wrap_l ? sv : qmax;
+#endif
+        }
+      }
+      const QT qnew = td_update(qsa, rw, qmax, k.alpha, k.gamma);
+      *((PIPE ? st_on : active) ? q + srow * kQPad + act : q_dummy) = qnew;
+#if P2PMG_ABLATE == 9 || P2PMG_ABLATE == 10
+      pat = Patch<QT>{0xFFFFFFFFu, 0, (QT)0};  // timing-only: the next step does not wait for this TD
+#else
+      pat = Patch<QT>{srow, act, qnew};  // rows issued before this store see the old value
+#endif
+    }
+    if constexpr (narrow) {
+      *reinterpret_cast<float2*>(__builtin_assume_aligned(rec_ptr, 8)) = make_float2(rw, cost);
+    } else {
+      const uint32_t bins = (p0.y & 0xFFFFu) | ((uint32_t)iT << 16);  // it * nT*nb + ib | iT << 16
+      float4* rp = reinterpret_cast<float4*>(__builtin_assume_aligned(rec_ptr, 16));
+      rp[0] = make_float4(rw, cost, g, pp);
+      rp[1] = make_float4(tin, __uint_as_float(acts), __uint_as_float(bins), __uint_as_float(ips));
+    }
+    rec_ptr += PIPE ? rec_adv : rec_step;
+    // step t's env row and pre-pass word are dead: step t + 3's into their slots (the barrier keeps
+    // the scheduler from hoisting the loads above the old values' last use, which would need a
+    // second register set and a copy at the loop's back edge)
+    asm volatile("" ::: "memory");
+    eS[P] = load_envv(envb + eo3);
+    pS[P] = preb[o3];
+    // avg_reward = sum_t mean_i r (community.py:179), canonical sequential order
+    const float m = group_sum<N>(rw, lane, i, sl, nullptr);
+    ep_sum = ep_sum + div_n_r<N>(m, rn);
+
+    tin = tin1;
+    tm = tm1;
+    iT = iT1;
+    o3 += (uint32_t)A;
+    o3 = o3 == TA ? 0u : o3;
+    eo3 += env_st;
+    eo3 = eo3 == env_end ? 0u : eo3;
+    strip = strip1;
+    cw = cw1;
+    a0 = a0n;
+    aN = aNn;
+    row0 = row0n;
+    rowN = rowNn;
+    if constexpr (CAND) {
+#pragma unroll
+      for (int b = 0; b < 3; ++b) cand[b] = candn[b];
+    }
+  };
+  using S0 = std::integral_constant<int, 0>;
+  using S1 = std::integral_constant<int, 1>;
+  using S2 = std::integral_constant<int, 2>;
+  if constexpr (!PIPE) {
+    for (int ep = 0; ep < n_chain; ++ep) {
+      begin_episode(ep);
+      __builtin_amdgcn_s_waitcnt(0);  // enter the loop with nothing in flight (static waits inside)
+      int t = 0;
+      for (; t + 3 <= T; t += 3) {
+        step(S0{});
+        step(S1{});
+        step(S2{});
+      }
+      if (t < T) step(S0{});
+      if (t + 1 < T) step(S1{});
+#if P2PMG_TRACE
+      if (threadIdx.x == 0 && (blockIdx.x == 0 || (int)blockIdx.x == n_cons / 2 || (int)blockIdx.x == n_cons - 1))
+        printf("TRACE blk %d/%d T %d: per step wait %.1f round0 %.1f waitcand %.1f round1 %.1f issue %.1f rest %.1f "
+               "(one stamp %.1f)\n",
+               (int)blockIdx.x, n_cons, T, (double)trW / T, (double)trA0 / T, (double)trWC / T, (double)trA1 / T,
+               (double)trC / T, (double)trR / (T - 1), (double)trCal / T);
+      trW = trC = trR = trLast = trA0 = trWC = trA1 = trMid = trCal = 0;
+#endif
+      end_episode(ep);
+    }  // chain
+    if (active) {
+      p.t_in[a] = tin;
+      p.t_m[a] = tm;
+      if constexpr (BAT != 0) p.soc[a] = soc;
+    }
+  } else {
+    // Phase ph (L = T / 2 lockstep steps; the launcher sends T % 6 == 0, so the ring's rotation holds
+    // across phases): episode ph runs its first half in half ph & 1 of the wave, episode ph - 1 its
+    // second half in the other.  A half without an episode (the upper one in phase 0, one of them in
+    // the last phase) runs masked to the dummy slots, as inactive lanes do.
+    const int L = T / 2;
+    int ep_l = grp == 0 ? 0 : -1;  // the episode this lane's half runs
+    st_on = active && grp == 0;
+    begin_episode(ep_l);  // the upper half: only its ring, rows and episode 1's T0 draw
+    __builtin_amdgcn_s_waitcnt(0);
+    for (int ph = 0;; ++ph) {
+      if (ph > 0) {
+        if (grp == (ph & 1)) {  // this half is at an episode boundary
+          if (st_on && i == 0) {
+            if (p.chain_rewards) p.chain_rewards[(size_t)ep_l * p.S + s] = ep_sum;
+            if (ep_l == n_chain - 1) p.ep_reward[s] = ep_sum;
+          }
+          if (ph <= n_chain) {
+            ep_l = ph;
+            st_on = active && ph < n_chain;
+            begin_episode(ph < n_chain ? ph : n_chain - 1);
+          }
+        }
+        // both halves enter the loop with nothing in flight (the other half's rows sit through this)
+        __builtin_amdgcn_s_waitcnt(0);
+        if (ph > n_chain) break;
+      }
+      wrap_l = st_on && grp != (ph & 1) && ep_l + 1 < n_chain;
+      for (int t = 0; t < L; t += 3) {
+        wrap_it = t + 3 >= L;
+        step(S0{});
+        step(S1{});
+        step(S2{});
+      }
+    }
+    // the T0 the chain leaves behind: drawn in the last episode's prologue
+    if (active && grp == ((n_chain - 1) & 1)) {
+      p.t_in[a] = t0_in;
+      p.t_m[a] = t0_m;
+    }
   }
 }
+
+// the community sizes the two-episodes-per-wave form is instantiated for (the plan asks the same)
+template <int N>
+constexpr bool kFastPipe = N == 2;
 
 // hipExtLaunchKernel stamps the start / stop events from the dispatch itself: no marker packets
 // between back-to-back episodes
 template <int N, typename QT, int R1, int BAT, bool NARROW>
 void launch_fast_nw(const EpisodeParams& p, const uint2* pre, FastRec* recs, int blocks, int spw, int prod,
                     const PrepOut& nxt, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
+  if constexpr (kFastPipe<N> && BAT == 0) {
+    if (p.mode == 0 && p.interleave)
+      return hipExtLaunchKernelGGL((episode_fast_kernel<N, QT, R1, true, BAT, NARROW, true>), dim3(blocks + prod),
+                                   dim3(kWave), 0, st, ev0, ev1, 0, p, pre, recs, spw, blocks, nxt);
+  }
   if (p.mode == 0)
     hipExtLaunchKernelGGL((episode_fast_kernel<N, QT, R1, true, BAT, NARROW>), dim3(blocks + prod), dim3(kWave), 0, st,
                           ev0, ev1, 0, p, pre, recs, spw, blocks, nxt);
@@ -609,6 +761,10 @@ template <int N, typename QT>
 hipError_t launch_fast_n(const EpisodeParams& p, const uint2* pre, void* recs, int spw, const PrepOut* nxt,
                          hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
   constexpr int G = pow2ceil(N);
+  // two episodes per wave need what the plan's interleave promises; anything else is a caller's error
+  if (p.interleave && !(kFastPipe<N> && p.mode == 0 && !p.battery && p.chain >= 2 && p.reset_t0 && p.T % 6 == 0 &&
+                        p.nT <= 32 && spw > 0 && spw <= kWave / 2 / G))
+    return hipErrorInvalidValue;
   if (spw <= 0 || spw > kWave / G) spw = kWave / G;
   const int blocks = (p.S + spw - 1) / spw;
   const size_t n = (size_t)p.T * p.A;

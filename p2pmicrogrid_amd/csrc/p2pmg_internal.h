@@ -75,6 +75,9 @@ struct EpisodeParams {
   // its code words at codes + k * codes_stride and writes its episode reward to
   // chain_rewards[k * S + s] (when non-null).  0 or 1: one episode.
   int chain;
+  // chained launch: episodes e and e + 1 of an agent run in the two halves of a wave, T / 2 steps
+  // apart (the plan's interleave; the kernel's PIPE form)
+  int interleave;
   size_t codes_stride;
   float* chain_rewards;
   int nt, nT, nb, np;
@@ -157,7 +160,7 @@ struct RcParams {
 // tile != 0: the LDS-tile form at any N (else registers for N in {1..8, 16}, tiles for the rest)
 hipError_t launch_episode(const EpisodeParams& p, int q_dtype, int tile, hipStream_t stream);
 // fast per-agent-table path: step pre-pass ([T][A] {balw, bins}; optionally the Philox code
-// words) + episode_fast_kernel (N <= 8, R + 1 <= 4, no battery, no shared table)
+// words) + episode_fast_kernel (N <= 8, R + 1 <= 4, or <= 2 with a battery, no shared table)
 // Where one step pre-pass writes: its buffers and the episode its Philox draws are for.
 constexpr int kMaxChain = 64;  // episodes per chained launch (their thresholds travel in the kernarg)
 struct PrepOut {
@@ -184,6 +187,10 @@ inline void eps_threshold(double eps, uint32_t& thr, int& all) {
   thr = all ? 0xFFFFFFFFu : (uint32_t)c;
 }
 hipError_t launch_step_prepass(const EpisodeParams& p, const PrepOut& o, hipStream_t stream);
+// *out = the hazard distance D of an interleaved chain over the pre-pass words pre [T][A]
+// (chain_lag_kernel); T <= kChainLagMaxT (the kernel is O(T^2) per agent)
+constexpr int kChainLagMaxT = 512;
+hipError_t launch_chain_lag(int T, int A, const uint2* pre, int* out, hipStream_t stream);
 // next != null: the launch also runs the step pre-pass of the next episode (episode p.episode + 1,
 // same epsilon) into *next, in extra workgroups beside the episode's own
 // ev0 / ev1: timing events stamped by the dispatch (hipExtLaunchKernel)

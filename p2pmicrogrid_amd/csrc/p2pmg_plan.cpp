@@ -31,7 +31,8 @@ bool fast_applies(const PlanFacts& c, const p2pmg_episode_args& args, const Over
 
 }  // namespace
 
-EpisodePlan plan_episode(const PlanFacts& c, const p2pmg_episode_args& args, bool chained, const Overrides& ov) {
+EpisodePlan plan_episode(const PlanFacts& c, const p2pmg_episode_args& args, bool chained, const Overrides& ov,
+                         int n_chain) {
   const p2pmg_config& g = c.cfg;
   const bool train = args.mode == P2PMG_MODE_TRAIN;
   const bool philox = train && args.rng == P2PMG_RNG_PHILOX;
@@ -64,6 +65,11 @@ EpisodePlan plan_episode(const PlanFacts& c, const p2pmg_episode_args& args, boo
   pl.packed_records = fast || sq16;
   pl.rec_narrow = (fast || sq16) && (args.record & ~(P2PMG_REC_REWARD | P2PMG_REC_COST)) == 0 ? 1 : 0;
   pl.speculate = fast && !ov.no_spec;
+  // two chained episodes per wave (episode_fast_kernel's PIPE form, instantiated for N = 2): the later
+  // episode starts from its own T0 draw (the reset), and the uploaded inputs keep the two episodes'
+  // table rows apart (chain_lag_ok)
+  pl.interleave = fast && chained && n_chain >= 2 && philox && (args.flags & P2PMG_FLAG_RESET_T0) != 0 && !c.battery &&
+                  c.T % 6 == 0 && g.n_temp_states <= 32 && c.N == 2 && c.chain_lag_ok && !ov.no_interleave;
   int spw = args.scen_per_wave > 0 ? args.scen_per_wave : ov.spw;
   if (spw <= 0) {  // automatic: full waves, or spread a small batch over all CUs (one wave per CU)
     const int full = 64 / (c.N <= 1 ? 1 : c.N <= 2 ? 2 : c.N <= 4 ? 4 : 8);
@@ -76,6 +82,7 @@ EpisodePlan plan_episode(const PlanFacts& c, const p2pmg_episode_args& args, boo
     if (fast && train && args.epsilon < 0.5 && waves < c.n_cu) spw = std::max(full / 4, (spw + 1) / 2);
     spw = std::min(spw, full);
   }
+  if (pl.interleave) spw = std::min(spw, 32 / 2);  // a scenario's lanes stay inside one half of the wave
   pl.spw = spw;
   return pl;
 }

@@ -17,6 +17,9 @@ struct PlanFacts {
   bool battery = false;
   bool roles = false;        // cfg.shared_q == P2PMG_SHARED_ROLE
   bool thermal_set = false;  // p2pmg_set_thermal uploaded values (false: the config's, where sq16 applies)
+  // the uploaded inputs' hazard distance D allows two chained episodes per wave, half an episode apart:
+  // D + 4 <= T / 2 (chain_lag_kernel in p2pmg_small.hip, once per upload)
+  bool chain_lag_ok = false;
 };
 
 // the environment overrides (the runtime reads them once per process)
@@ -24,6 +27,7 @@ struct Overrides {
   bool general = false;  // P2PMG_KERNEL=general: neither the fast nor the sq16 kernel
   int spw = 0;           // P2PMG_SPW: scenarios per wave where the arguments leave it automatic
   bool no_spec = false;  // P2PMG_NO_SPEC=1 (profiling only): no producer blocks, so the episode kernel's counters are its own
+  bool no_interleave = false;  // P2PMG_INTERLEAVE=0 (A/B runs): chained launches run their episodes one after the other
 };
 
 enum class Family { General, Tile, Fast, Sq16 };  // Tile: the general kernel's LDS-tile form
@@ -37,9 +41,12 @@ struct EpisodePlan {
   int rec_narrow = 0;           // fast / sq16: only {reward, cost} requested -> 8-B record rows
   bool packed_records = false;  // the launch writes packed rows (rec_pack) and stamps its own timing events
   bool speculate = false;       // fast: extra workgroups compute the next launch's pre-pass
+  bool interleave = false;      // fast, chained: episodes e and e + 1 of an agent in the two halves of a wave, T / 2 steps apart
   const char* error = nullptr;  // the request is refused (P2PMG_E_INVALID) with this message
 };
 
-EpisodePlan plan_episode(const PlanFacts& c, const p2pmg_episode_args& args, bool chained, const Overrides& ov);
+// n_chain: the episodes of a chained launch
+EpisodePlan plan_episode(const PlanFacts& c, const p2pmg_episode_args& args, bool chained, const Overrides& ov,
+                         int n_chain = 1);
 
 }  // namespace p2pmg

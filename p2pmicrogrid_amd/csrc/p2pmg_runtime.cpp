@@ -147,6 +147,11 @@ struct p2pmg_ctx : p2pmg::PlanFacts {
   long long spec_version[2] = {-1, -1};
   long long inputs_version = 0;  // bumped by every input upload (env, profiles, max_in, hp levels)
   long long spec_hits = 0, spec_misses = 0;  // fast-path launches whose pre-pass was / was not ready
+  // hazard distance of an interleaved chain over the uploaded inputs (launch_chain_lag), computed by
+  // the first chained launch after an upload; chain_lag_ok (PlanFacts) is its verdict
+  DevBuf<int> d_lag;
+  int chain_lag = -1;            // -1: not computed (T > kChainLagMaxT)
+  long long lag_version = -1;    // inputs_version it was computed for
   DevBuf<char> dummy;        // fast path: target of masked-off stores (2 * 64 * 32 B)
   DevBuf<char> rec_pack;     // fast path: packed records [T][A] x 32 B
   int code_src = 0;          // what the code buffer holds: 0 none, 1 replay upload, 2 Philox pre-pass
@@ -288,7 +293,8 @@ int ensure_records(p2pmg_ctx* c, int mask) {
 const p2pmg::Overrides& overrides() {
   static const p2pmg::Overrides ov = [] {
     const char *k = getenv("P2PMG_KERNEL"), *w = getenv("P2PMG_SPW"), *n = getenv("P2PMG_NO_SPEC");
-    return p2pmg::Overrides{k && !strcmp(k, "general"), w ? atoi(w) : 0, n && atoi(n) != 0};
+    const char* il = getenv("P2PMG_INTERLEAVE");
+    return p2pmg::Overrides{k && !strcmp(k, "general"), w ? atoi(w) : 0, n && atoi(n) != 0, il && atoi(il) == 0};
   }();
   return ov;
 }
@@ -844,6 +850,22 @@ static int prepare_general(p2pmg_ctx* c, const p2pmg_episode_args* args, const E
   return P2PMG_OK;
 }
 
+// The hazard distance of the uploaded inputs, from the pre-pass words the launch is about to read: one
+// small kernel and a 4-byte read-back per upload (the inputs stay put between launches in real use).
+static int update_chain_lag(p2pmg_ctx* c, const uint2* pre) {
+  if (c->lag_version == c->inputs_version) return P2PMG_OK;
+  c->chain_lag = -1;
+  if (c->T <= p2pmg::kChainLagMaxT) {
+    if (!c->d_lag) HIP_TRY(c, c->d_lag.alloc(1));
+    HIP_TRY(c, p2pmg::launch_chain_lag(c->T, c->A, pre, c->d_lag, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&c->chain_lag, c->d_lag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  c->chain_lag_ok = c->chain_lag >= 0 && c->chain_lag + 4 <= c->T / 2;
+  c->lag_version = c->inputs_version;
+  return P2PMG_OK;
+}
+
 // validate -> plan -> prepare the plan's family -> launch -> finish_launch
 static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const ChainReq* ch) {
   if (!c || !args) return P2PMG_E_INVALID;
@@ -855,7 +877,7 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
   if (train && args->rng != P2PMG_RNG_REPLAY && args->rng != P2PMG_RNG_PHILOX) return fail(c, P2PMG_E_INVALID, "rng");
   if (train && args->rng == P2PMG_RNG_REPLAY && !c->have_codes)
     return fail(c, P2PMG_E_STATE, "run_episode: replay mode needs p2pmg_set_replay_codes");
-  const EpisodePlan plan = p2pmg::plan_episode(*c, *args, ch != nullptr, overrides());
+  EpisodePlan plan = p2pmg::plan_episode(*c, *args, ch != nullptr, overrides(), ch ? ch->n : 1);
   if (plan.error) return fail(c, P2PMG_E_INVALID, plan.error);
   const p2pmg_config& g = c->cfg;
   const bool fast = plan.family == Family::Fast, sq16 = plan.family == Family::Sq16, tile = plan.family == Family::Tile;
@@ -864,6 +886,11 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
   const int ps = c->pslot;
   p2pmg::PrepOut next{};
   RC_TRY(fast ? prepare_fast(c, args, ch, plan, p, &next) : sq16 ? prepare_sq16(c, args, p) : prepare_general(c, args, plan, p));
+  if (fast && ch && c->lag_version != c->inputs_version) {  // the first chained launch after an upload
+    RC_TRY(update_chain_lag(c, c->pre[ps]));
+    plan = p2pmg::plan_episode(*c, *args, true, overrides(), ch->n);  // ... with the fact it was missing
+  }
+  p.interleave = plan.interleave ? 1 : 0;
   p.rec_narrow = plan.rec_narrow;
   const bool reset = (args->flags & P2PMG_FLAG_RESET_T0) != 0;
   p.reset_t0 = (ext && reset) ? 1 : 0;
@@ -887,7 +914,8 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
                     std::to_string(c->N) + (tile ? ",tile" + std::to_string(p2pmg::general_tile_cap(c->N)) : "") + "," +
                     (g.q_dtype == 0 ? "f64" : "f32") + ",R1=" + std::to_string(c->R + 1) +
                     (ext ? (train ? ",train" : ",greedy") : "") + (g.shared_q ? ",shared" : "") + (c->roles ? ",roles" : "") +
-                    (c->battery ? (ext && !p.bat_safe ? ",battery,range-checked>" : ",battery>") : ">"),
+                    (c->battery ? (ext && !p.bat_safe ? ",battery,range-checked>" : ",battery>")
+                                : plan.interleave ? ",interleaved>" : ">"),
                 args->record, ext ? (args->record & 127) : 0, plan.rec_narrow);
   return P2PMG_OK;
 }
@@ -942,6 +970,15 @@ int p2pmg_get_episode_rewards(p2pmg_ctx* c, int n, float* host) {
   if (n > c->chain_n) return fail(c, P2PMG_E_STATE, "get_episode_rewards: the last run_episodes call ran fewer episodes");
   HIP_TRY(c, hipMemcpyAsync(host, c->chain_rew, (size_t)n * c->S * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return P2PMG_OK;
+}
+
+int p2pmg_chain_lag(p2pmg_ctx* c, int* distance, int* safe) {
+  if (!c) return P2PMG_E_INVALID;
+  if (c->lag_version != c->inputs_version)
+    return fail(c, P2PMG_E_STATE, "chain_lag: no chained launch has run since the last input upload");
+  if (distance) *distance = c->chain_lag;
+  if (safe) *safe = c->chain_lag_ok ? 1 : 0;
   return P2PMG_OK;
 }
 

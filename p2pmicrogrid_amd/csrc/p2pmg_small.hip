@@ -86,6 +86,32 @@ __global__ void step_prepass_kernel(const EpisodeParams p, const PrepOut o) {
   prepass_one(p, o, k, (int)blockIdx.y);  // blockIdx.y: the chain's episode (uniform per workgroup)
 }
 
+// Hazard distance of an interleaved chain (episode_fast_kernel's PIPE form), from the pre-pass words:
+// step u of an agent's earlier episode and step v of its later one conflict when they touch rows of
+// one (time bin, balance bin) key with a write involved: lo(u) == lo(v) (the step's own rows, read
+// and written), lo(u) == hi(v) or hi(u) == lo(v) (hi: the next-state row, read only).  Step T - 1's
+// next-state read alone does not count: the kernel serves it from a snapshot.  *out = max u - v over
+// every agent's conflicting pairs (atomicMax; the caller presets it to 0, what u == v gives).
+// One thread per agent, O(T^2) compares, the words read through the caches.
+__global__ void chain_lag_kernel(int T, int A, const uint2* __restrict__ pre, int* __restrict__ out) {
+  const int a = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (a >= A) return;
+  int best = 0;
+  for (int u = T - 1; u > best; --u) {
+    const uint32_t wu = pre[(size_t)u * A + a].y;
+    const uint32_t lu = wu & 0xFFFFu, hu = u == T - 1 ? 0xFFFFFFFFu : wu >> 16;
+    for (int v = 0; v < u - best; ++v) {
+      const uint32_t wv = pre[(size_t)v * A + a].y;
+      const uint32_t lv = wv & 0xFFFFu, hv = wv >> 16;
+      if (lu == lv || lu == hv || hu == lv) {
+        best = u - v;
+        break;
+      }
+    }
+  }
+  atomicMax(out, best);
+}
+
 // FastRec rows -> the general record buffers (reward, cost, grid, p2p, tin [T][A]; action u8 and
 // packed index i32 [T][R+1][A]), for the records the caller asks for
 __global__ void fast_rec_unpack_kernel(int T, int R1, int A, uint32_t tb, const FastRec* __restrict__ recs, int narrow,
@@ -407,6 +433,13 @@ hipError_t launch_step_prepass(const EpisodeParams& p, const PrepOut& o, hipStre
   const size_t n = (size_t)p.T * p.A;
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(step_prepass_kernel, dim3(grid_for(n, 256), o.n_ep > 1 ? o.n_ep : 1), dim3(256), 0, stream, p, o);
+  return hipGetLastError();
+}
+
+hipError_t launch_chain_lag(int T, int A, const uint2* pre, int* out, hipStream_t stream) {
+  const hipError_t e = hipMemsetAsync(out, 0, sizeof(int), stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(chain_lag_kernel, dim3(grid_for((size_t)A, 64)), dim3(64), 0, stream, T, A, pre, out);
   return hipGetLastError();
 }
 

@@ -370,6 +370,14 @@ class DeviceCommunityBatch:
         self._chk(self.L.p2pmg_prepass_stats(self._ctx, C.byref(h), C.byref(m)), "prepass_stats")
         return int(h.value), int(m.value)
 
+    def chain_lag(self):
+        """(D, safe): the hazard distance of the uploaded inputs and whether chained launches may run two
+        episodes per wave (D + 4 <= T / 2; p2pmg_chain_lag).  Known after the first run_episodes since
+        the last upload; D = -1 where it is not computed (T > 512)."""
+        d, ok = C.c_int(0), C.c_int(0)
+        self._chk(self.L.p2pmg_chain_lag(self._ctx, C.byref(d), C.byref(ok)), "chain_lag")
+        return int(d.value), bool(ok.value)
+
     def last_kernel(self) -> str:
         """Name of the kernel the last episode launch ran (fast or general path)."""
         return (self.L.p2pmg_last_kernel(self._ctx) or b"").decode()
