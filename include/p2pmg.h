@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag) */
+#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag, p2pmg_set_learning, p2pmg_get_learning, p2pmg_run_episodes_eps) */
 
 typedef struct p2pmg_ctx p2pmg_ctx;
 
@@ -86,8 +86,8 @@ typedef struct p2pmg_config {
   int32_t n_balance_states; /* 20 */
   int32_t n_p2p_states;     /* 20 */
   int32_t n_actions;        /* 3 (<= 4) */
-  double alpha;             /* 1e-5 (rl.py:60) */
-  double gamma;             /* 0.9  (rl.py:59) */
+  double alpha;             /* 1e-5 (rl.py:60); per agent: p2pmg_set_learning */
+  double gamma;             /* 0.9  (rl.py:59); per agent: p2pmg_set_learning */
   float hp_levels[4];       /* f32(level * max_power) = {0, 1500, 3000} W (agent.py:268, heating.py:124) */
   float setpoint;           /* 21 (community.py:226) */
   float temp_margin;        /* 1  (heating.py:90) */
@@ -104,7 +104,7 @@ typedef struct p2pmg_config {
   /* costs (community.py:63) and reward (agent.py:230) */
   float minutes_per_hour; /* 60 */
   float kilo;             /* f32(1e-3) */
-  float penalty_weight;   /* 10 */
+  float penalty_weight;   /* 10; per agent: p2pmg_set_learning */
   uint64_t seed;          /* Philox key */
   int64_t scenario_offset; /* global index of this context's scenario 0 (multi-GPU sharding):
                               Philox counters use global agent ids so results do not depend
@@ -219,7 +219,24 @@ int p2pmg_run_episode(p2pmg_ctx* ctx, const p2pmg_episode_args* args);
  * same as this call's last).  p2pmg_get_episode_reward returns the last episode's reward. */
 int p2pmg_run_episodes(p2pmg_ctx* ctx, const p2pmg_episode_args* args, int n, const double* epsilons, int next_n,
                        const double* next_epsilons);
-/* [n][S] episode rewards (community.py:179) of the first n episodes of the last p2pmg_run_episodes call */
+/* p2pmg_run_episodes with one epsilon per SCENARIO: scenario s explores at eps[k][s] in episode
+ * args->episode + k (eps is [n][S]); args->epsilon is ignored.  The agents of one community share
+ * their decay schedule (community.py:285-286; QActor.decay rl.py:83-87), so a batch of communities at
+ * different points of different schedules (a sweep) is one call.  P2PMG_MODE_TRAIN with
+ * P2PMG_RNG_PHILOX only, anything else P2PMG_E_INVALID (replay codes already carry each agent's own
+ * epsilon); every value finite and in [0, 1], else P2PMG_E_INVALID.  The rule is p2pmg_run_episode's,
+ * per scenario: word w explores iff w < ceil(eps 2^32) (eps = 1: every word), and below eps = 2^-8 the
+ * action comes from its own Philox block.  The thresholds travel in a device table [n][S] that the
+ * step pre-pass, the code-word pre-pass and the general kernel's in-kernel draws read; chained and
+ * interleaved launches are planned as for p2pmg_run_episodes, and calls of more than 64 episodes split
+ * the same way.  With every row one repeated value the call equals p2pmg_run_episodes at that
+ * schedule, bit for bit.  The call does not speculate the next call's pre-pass and leaves no
+ * speculative slot valid, so the next plain launch computes its own.  A shared-table N = 16 context
+ * runs the general kernel's shared-table form for this call, not episode_sq16_kernel.
+ * p2pmg_get_episode_rewards works as after p2pmg_run_episodes.  DQN contexts: P2PMG_E_UNSUPPORTED. */
+int p2pmg_run_episodes_eps(p2pmg_ctx* ctx, const p2pmg_episode_args* args, int n, const double* eps /* [n][S] */);
+/* [n][S] episode rewards (community.py:179) of the first n episodes of the last p2pmg_run_episodes or
+ * p2pmg_run_episodes_eps call */
 int p2pmg_get_episode_rewards(p2pmg_ctx* ctx, int n, float* host);
 /* one P2PMG_REC_* bit of the LAST episode launch; P2PMG_E_STATE if that launch did not record it */
 int p2pmg_get_record(p2pmg_ctx* ctx, int which, void* host);
@@ -319,6 +336,19 @@ int p2pmg_get_hp_levels(p2pmg_ctx* ctx, float* levels /* [A][3] */);
  * instead of episode_sq16_kernel (same results, bit for bit) until NULL restores the config's. */
 int p2pmg_set_thermal(p2pmg_ctx* ctx, const float* params);
 int p2pmg_get_thermal(p2pmg_ctx* ctx, float* params);
+/* per-agent learner constants: each QActor's own alpha and gamma (rl.py:58-71, used in QActor.train
+ * rl.py:125-128) and the comfort weight of the agent's reward (agent.py:225-232).  Each argument is [A],
+ * or NULL for the config's value of that field; all three NULL restores the config's values.  Values
+ * must be finite with 0 <= alpha <= 1, 0 <= gamma <= 1 and penalty_weight >= 0, else P2PMG_E_INVALID,
+ * and a rejected call changes nothing.  Every tabular episode kernel and p2pmg_q_calls read these
+ * (f32 tables cast alpha and gamma to f32 in the kernel, as before); p2pmg_create fills them from the
+ * config, so a context that never calls this computes the same bits as with the broadcast constants.
+ * A shared-table N = 16 context with values set here runs the general kernel's shared-table form
+ * instead of episode_sq16_kernel (same results, bit for bit) until the all-NULL call restores the
+ * config's.  DQN contexts: P2PMG_E_UNSUPPORTED (the DQN's gamma is p2pmg_dqn_config.gamma). */
+int p2pmg_set_learning(p2pmg_ctx* ctx, const double* alpha, const double* gamma, const float* penalty_weight);
+/* the values in use, each [A]; any output may be NULL */
+int p2pmg_get_learning(p2pmg_ctx* ctx, double* alpha, double* gamma, float* penalty_weight);
 /* Battery per agent (storage.py:36-76, rule agent.py:138-153, f64): capacity [A] in J (0 = none;
  * NULL disables storage), SoC bounds, round-trip efficiency, initial SoC [A] (NULL = 0.5). */
 int p2pmg_set_battery(p2pmg_ctx* ctx, const double* capacity, double min_soc, double max_soc,
@@ -352,7 +382,8 @@ int p2pmg_table_hash_allgather(p2pmg_ctx* ctx, uint64_t* out);
  * by one device thread: for entry k, s = indices(s_obs[k]); a = codes[k] == P2PMG_GREEDY ?
  * argmax Q[agent[k], s] (first max) : codes[k]; q_out[k] = greedy ? Q[s, a] : 0 (select_action /
  * greedy_action); if train, Q[s, a] += alpha * ((reward[k] + gamma * max Q[ns]) - Q[s, a])
- * (QActor.train).  ns_obs/rewards may be NULL when train == 0. */
+ * (QActor.train), alpha and gamma being agent[k]'s own (p2pmg_set_learning).  ns_obs/rewards may be
+ * NULL when train == 0. */
 int p2pmg_q_calls(p2pmg_ctx* ctx, int n, const int32_t* agents, const float* s_obs /* [n][4] */,
                   const uint8_t* codes, const float* rewards, const float* ns_obs /* [n][4] */,
                   int train, int32_t* actions_out, double* q_out);

@@ -44,6 +44,7 @@ EXPORTS = [
     "p2pmg_run_episodes", "p2pmg_get_episode_rewards", "p2pmg_chain_lag",
     "p2pmg_set_thermal", "p2pmg_get_thermal", "p2pmg_rc_step_ex", "p2pmg_get_hp_levels",
     "p2pmg_episode_summary",
+    "p2pmg_set_learning", "p2pmg_get_learning", "p2pmg_run_episodes_eps",
 ]
 
 
@@ -118,6 +119,7 @@ def _declare(lib):
         "p2pmg_get_q": ([vp, i32, i32, vp, i32], i32),
         "p2pmg_run_episode": ([vp, C.POINTER(EpisodeArgs)], i32),
         "p2pmg_run_episodes": ([vp, C.POINTER(EpisodeArgs), i32, dp, i32, vp], i32),
+        "p2pmg_run_episodes_eps": ([vp, C.POINTER(EpisodeArgs), i32, dp], i32),  # eps [n][S] f64
         "p2pmg_get_episode_rewards": ([vp, i32, fp], i32),
         "p2pmg_get_record": ([vp, i32, vp], i32),
         "p2pmg_get_episode_reward": ([vp, fp], i32),
@@ -137,6 +139,8 @@ def _declare(lib):
         "p2pmg_get_hp_levels": ([vp, fp], i32),
         "p2pmg_set_thermal": ([vp, vp], i32),
         "p2pmg_get_thermal": ([vp, fp], i32),
+        "p2pmg_set_learning": ([vp, vp, vp, vp], i32),  # alpha [A] f64, gamma [A] f64, penalty_weight [A] f32; NULL = config
+        "p2pmg_get_learning": ([vp, vp, vp, vp], i32),
         "p2pmg_run_rule_episode": ([vp, i32], i32),
         "p2pmg_set_hp_state": ([vp, fp], i32),
         "p2pmg_get_hp_state": ([vp, fp], i32),

@@ -46,6 +46,14 @@ def thermal_arrays(agents) -> Tuple[np.ndarray, np.ndarray]:
     return levels, params
 
 
+def learning_arrays(agents) -> Tuple[np.ndarray, np.ndarray]:
+    """Each agent's own QActor learning rate and discount (rl.py:58-71): (alpha [N], gamma [N]) f64,
+    what DeviceCommunityBatch.set_learning takes.  Pure NumPy."""
+    alpha = np.array([float(a.actor._alpha) for a in agents], np.float64)
+    gamma = np.array([float(a.actor._gamma) for a in agents], np.float64)
+    return alpha, gamma
+
+
 class CommunityMicrogrid:
 
     def __init__(self, timeline, agents: List[ActingAgent], rounds: int, q_dtype: Optional[str] = None,
@@ -142,6 +150,14 @@ class CommunityMicrogrid:
             eng.set_thermal(params[None, :, 0], cop=params[None, :, 3], lower=params[None, :, 1],
                             upper=params[None, :, 2])
             self._uploaded["thermal"] = thermal_key
+        if not (self._dqn or self._rule):
+            # every actor's own alpha and gamma, keyed on the values like the thermal arrays: a change
+            # between episodes (actor._alpha = ...) is uploaded again
+            alpha, gamma = learning_arrays(self.agents)
+            learning_key = (alpha.tobytes(), gamma.tobytes())
+            if self._uploaded.get("learning") != learning_key:
+                eng.set_learning(alpha=alpha[None], gamma=gamma[None])
+                self._uploaded["learning"] = learning_key
         return eng
 
     def _push_temperatures(self, eng):
@@ -284,6 +300,8 @@ class CommunityMicrogrid:
             eng.set_hp_levels(np.broadcast_to(levels, (D, N, 3)))
             par = np.broadcast_to(params, (D, N, 4))
             eng.set_thermal(par[..., 0], cop=par[..., 3], lower=par[..., 1], upper=par[..., 2])
+            alpha, gamma = learning_arrays(self.agents)
+            eng.set_learning(alpha=np.broadcast_to(alpha, (D, N)), gamma=np.broadcast_to(gamma, (D, N)))
             eng.set_temperatures(stack("t_in", (N,)), stack("t_m", (N,)))
             rec = ("grid", "p2p", "cost", "t_in", "action")
             eng.run_episode("greedy", record=rec)

@@ -94,9 +94,10 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
   const int s_env = p.n_env == 1 ? 0 : (active ? s : 0);
   const int T = p.T;
   const size_t A = (size_t)p.A;
-  // the agent's setpoint, comfort band and COP: loaded here, before the chain loop, with hp_lv[a],
-  // max_in[a] and t_in[a]; the step loop reads them as the VGPRs the pinned arguments were
-  const KC k = pin_constants(p, p.thermal[a]);
+  // the agent's setpoint, comfort band and COP, and its learner's alpha, gamma and comfort weight:
+  // loaded here, before the chain loop, with hp_lv[a], max_in[a] and t_in[a]; the step loop reads them
+  // as the VGPRs the pinned arguments were
+  const KC k = pin_constants(p, p.thermal[a], p.learn[a]);
   const uint32_t n_states = (uint32_t)(p.nt * p.nT * p.nb * p.np);
   QT* __restrict__ q = reinterpret_cast<QT*>(p.q) + (size_t)a * n_states * kQPad;  // TD stores
   // Row gathers as ONE 32-bit offset from the wave's first table (global_load's SGPR-base + VGPR-offset

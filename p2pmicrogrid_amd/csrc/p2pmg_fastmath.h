@@ -131,6 +131,11 @@ __device__ __forceinline__ void prepass_one(const EpisodeParams& p, const PrepOu
     q.eps = o.eps;
     q.eps_thr = chain ? o.ep_thr[ep] : o.eps_thr;
     q.eps_all = chain ? (int)((o.ep_all >> ep) & 1u) : o.eps_all;
+    if (o.eps_tab) {  // the scenario's own threshold of this episode (p2pmg_run_episodes_eps)
+      const uint2 e = o.eps_tab[(size_t)ep * p.S + a / p.N];
+      q.eps_thr = e.x;
+      q.eps_all = (int)e.y;
+    }
     const int R1 = p.R + 1, W = (R1 + 3) >> 2;
     const uint32_t gid = p.agent_offset + (uint32_t)a;
     const uint64_t codes = philox_codes_of(q, t, gid);

@@ -66,11 +66,11 @@ __device__ __forceinline__ float group_sum_n(float v, int i, int sl, int n, floa
 // exploration code of round r >= 8 of step t (the 64-bit code word holds rounds 0..7): the replay
 // word (r / 4) of the step, or Philox word k = t (R + 1) + r (p2pmg_device.h, oracle/philox.py)
 __device__ __forceinline__ int late_code(const EpisodeParams& p, const uint32_t* codes_a, size_t step_off, int t,
-                                         int r, int a, bool active) {
+                                         int r, int a, bool active, const EpsThr& e) {
   if (p.mode != 0 || !active) return 255;
   if (p.rng == 1)
-    return (int)philox_round_code(t, p.R + 1, r, (uint32_t)p.episode, p.agent_offset + (uint32_t)a, p.eps_thr,
-                                  p.eps_all, p.seed_lo, p.seed_hi);
+    return (int)philox_round_code(t, p.R + 1, r, (uint32_t)p.episode, p.agent_offset + (uint32_t)a, e.thr, e.all,
+                                  p.seed_lo, p.seed_hi);
   return (int)((codes_a[step_off + (size_t)(r >> 2) * p.A] >> (8 * (r & 3))) & 0xFFu);
 }
 // workgroup shape of the general kernel: one wave, or (shared table) kSqWaves waves around one LDS
@@ -124,9 +124,11 @@ __global__ __launch_bounds__((kWave * general_wpb<NC, WIDE, SQ>())) void episode
   const bool margin_one = p.margin == 1.0f;
   const uint32_t rec = (uint32_t)p.record;
   const size_t A = (size_t)p.A;
-  // loop constants in VGPRs (no SGPR spill reloads on the chain); setpoint, comfort band and COP are
-  // the agent's own (inactive and out-of-group lanes: agent 0's)
-  const KC k = pin_constants(p, p.thermal[a]);
+  // loop constants in VGPRs (no SGPR spill reloads on the chain); setpoint, comfort band, COP, alpha,
+  // gamma and the comfort weight are the agent's own (inactive and out-of-group lanes: agent 0's)
+  const KC k = pin_constants(p, p.thermal[a], p.learn[a]);
+  // the scenario's explore threshold for the in-kernel Philox draws (its own under p2pmg_run_episodes_eps)
+  const EpsThr ethr = eps_of(p, active ? s : 0);
   const Dims<B20> D{k.nt, k.nT, k.nb, k.np};
   std::conditional_t<WIDE, PTile<NC>, PRegs<NC>> P;
   if constexpr (WIDE) {
@@ -195,7 +197,7 @@ __global__ __launch_bounds__((kWave * general_wpb<NC, WIDE, SQ>())) void episode
   const float2 f0 = prof_at(0);
   float2 f1 = prof_at(f1o);
   StepIdx st = make_step(k, D, margin_one, e0.time, e1.time, FDIV(f0.x - f0.y, mi), f1, tin, mi, ip_zero);
-  uint64_t cw = code_word(p, step_codes(p, codes_a, 0, 0, a, W), active);
+  uint64_t cw = code_word(p, step_codes(p, codes_a, 0, 0, a, W, ethr), active);
   // Q rows are loaded unconditionally (a load under a divergent branch is waited for at the
   // join, which would serialise the prefetch); a row that is not needed aliases one that is
   // loaded anyway, so it costs no HBM traffic.  Inactive lanes read agent 0's table.
@@ -220,7 +222,7 @@ __global__ __launch_bounds__((kWave * general_wpb<NC, WIDE, SQ>())) void episode
     const EnvRow e2 = load_env(envb + e2o);
     const float2 f2 = prof_at(f2o);
 #endif
-    const CodeWords cw1r = step_codes(p, codes_a, c1o, t + 1 == T ? 0 : t + 1, a, W);
+    const CodeWords cw1r = step_codes(p, codes_a, c1o, t + 1 == T ? 0 : t + 1, a, W, ethr);
 
     P.clear();
     int act = 0, ip = ip_zero;
@@ -231,7 +233,7 @@ __global__ __launch_bounds__((kWave * general_wpb<NC, WIDE, SQ>())) void episode
     Row4<QT> rowR = row0;  // Q row of the final round's state (TD target Q[s, a])
 
     for (int r = 0; r < R1; ++r) {
-      const int code = r < 8 ? (int)((cw >> (8 * r)) & 0xFF) : late_code(p, codes_a, tA * W, t, r, a, active);
+      const int code = r < 8 ? (int)((cw >> (8 * r)) & 0xFF) : late_code(p, codes_a, tA * W, t, r, a, active, ethr);
       if (r > 0) {
         P.next_round();  // Jacobi: read the previous round's column (community.py:84-86)
         // powers = -P[:, i] with the diagonal zeroed (community.py:76,81); p2p = mean / max_in (agent.py:203)

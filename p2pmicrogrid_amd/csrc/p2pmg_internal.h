@@ -21,6 +21,13 @@ constexpr double kDeltaScale = 1099511627776.0;  // 2^40: shared-table TD deltas
 // (blocks are dealt round-robin over the 8 XCDs); the copies are folded before use
 constexpr int kDeltaCopies = 8;
 
+// One agent's learner constants, a 32-B row (p2pmg_set_learning): two 16-B loads in a kernel's prologue
+struct LearnRow {
+  double alpha, gamma;
+  float penw, pad[3];
+};
+static_assert(sizeof(LearnRow) == 32, "learning rows are 32 bytes");
+
 // Everything the episode kernel needs, passed by value in the kernarg segment.
 struct EpisodeParams {
   int S, N, R, T, A;
@@ -64,6 +71,13 @@ struct EpisodeParams {
   // Every kernel but episode_sq16_kernel reads these, not the scalars below (which fill the array
   // at p2pmg_create and stay the sq16 kernel's SGPR constants).
   const float4* thermal;
+  // [A] per-agent learner constants (QActor's own alpha and gamma, rl.py:58-71, and the agent's comfort
+  // weight): every tabular kernel but episode_sq16_kernel reads these, not alpha / gamma / penw below
+  // (which fill the array at p2pmg_create and stay the sq16 kernel's constants)
+  const LearnRow* learn;
+  // per-scenario exploration thresholds of this launch (p2pmg_run_episodes_eps): [chain rows][S]
+  // {eps_thr, eps_all}, row k for episode + k; null: eps_thr / eps_all above for every scenario
+  const uint2* eps_tab;
   void* dummy;               // >= 2 * kWave * 32 B scratch: target of the fast kernel's masked-off stores
   uint32_t* pre_ipc;         // fast path, N = 2: [T][A] round-1 p2p bins for the partner's 3 round-0 actions
   void* rec_pack;            // fast paths: packed records [T][A] x 32 B
@@ -177,6 +191,8 @@ struct PrepOut {
   size_t words_stride;
   uint32_t ep_thr[kMaxChain];
   uint64_t ep_all;
+  // per-scenario thresholds [n_ep][S] {thr, all} (p2pmg_run_episodes_eps); null: the values above
+  const uint2* eps_tab;
 };
 // w / 2^32 < eps  <=>  w < ceil(eps * 2^32) for every 32-bit w (w / 2^32 and eps * 2^32 are exact in
 // f64): thr = that ceiling, clamped to [0, 2^32]; all = (thr == 2^32), when every w explores
@@ -281,7 +297,7 @@ struct QCallParams {
   void* q;
   uint32_t n_states;
   int nt, nT, nb, np;
-  double alpha, gamma;
+  const LearnRow* learn;  // [A], indexed by agents[k]
 };
 hipError_t launch_q_calls(const QCallParams& p, hipStream_t stream);
 hipError_t launch_metrics(int S, const float* ep, double* out, hipStream_t stream);

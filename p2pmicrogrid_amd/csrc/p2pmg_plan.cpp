@@ -48,6 +48,7 @@ EpisodePlan plan_episode(const PlanFacts& c, const p2pmg_episode_args& args, boo
                     host_div_range(g.temp_margin) && g.n_time_states == 20 && g.n_temp_states == 20 &&
                     g.n_balance_states == 20 && g.n_p2p_states == 20 &&
                     !c.thermal_set &&  // per-agent thermal parameters: the general kernel's shared-table form
+                    !c.learning_set && !c.eps_table &&  // ... as for per-agent learner constants, per-scenario epsilon
                     !(args.flags & (P2PMG_FLAG_GENERAL_KERNEL | P2PMG_FLAG_TILE_KERNEL)) && !ov.general;
   // the general kernel's LDS-tile form: every N outside {1..8, 16}, or any N on request
   const bool tile = !fast && !sq16 &&
@@ -64,7 +65,7 @@ EpisodePlan plan_episode(const PlanFacts& c, const p2pmg_episode_args& args, boo
   pl.want_ipc = fast && c.N == 2 && c.R >= 1 && !c.battery;
   pl.packed_records = fast || sq16;
   pl.rec_narrow = (fast || sq16) && (args.record & ~(P2PMG_REC_REWARD | P2PMG_REC_COST)) == 0 ? 1 : 0;
-  pl.speculate = fast && !ov.no_spec;
+  pl.speculate = fast && !ov.no_spec && !c.eps_table;
   // two chained episodes per wave (episode_fast_kernel's PIPE form, instantiated for N = 2): the later
   // episode starts from its own T0 draw (the reset), and the uploaded inputs keep the two episodes'
   // table rows apart (chain_lag_ok)

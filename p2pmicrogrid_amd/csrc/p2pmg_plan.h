@@ -17,6 +17,10 @@ struct PlanFacts {
   bool battery = false;
   bool roles = false;        // cfg.shared_q == P2PMG_SHARED_ROLE
   bool thermal_set = false;  // p2pmg_set_thermal uploaded values (false: the config's, where sq16 applies)
+  bool learning_set = false;  // p2pmg_set_learning uploaded values (false: the config's, where sq16 applies)
+  // the launch belongs to a p2pmg_run_episodes_eps call: thresholds per scenario from a device table
+  // (no sq16 kernel, no speculative pre-pass for the next launch)
+  bool eps_table = false;
   // the uploaded inputs' hazard distance D allows two chained episodes per wave, half an episode apart:
   // D + 4 <= T / 2 (chain_lag_kernel in p2pmg_small.hip, once per upload)
   bool chain_lag_ok = false;

@@ -163,6 +163,10 @@ struct p2pmg_ctx : p2pmg::PlanFacts {
   DevBuf<double> sum_agent, sum_scen;  // p2pmg_episode_summary: [A][16] and [S][16], allocated on first use
   DevBuf<float4> hp_lv;      // [A] per-agent heat-pump levels
   DevBuf<float4> thermal;    // [A] per-agent {setpoint, lower bound, upper bound, COP} (p2pmg_set_thermal)
+  DevBuf<p2pmg::LearnRow> learn;  // [A] per-agent {alpha, gamma, comfort weight} (p2pmg_set_learning)
+  std::vector<p2pmg::LearnRow> h_learn;  // its host copy (p2pmg_get_learning, partial updates)
+  DevBuf<uint2> eps_tab;     // p2pmg_run_episodes_eps: [n][S] {threshold, explore-all} of the call
+  const uint2* eps_cur = nullptr;  // ... the rows of the launch being prepared (eps_table, PlanFacts)
   DevBuf<float> hp_on;       // [A] RuleAgent heat-pump state (lazily allocated, starts off)
   DevBuf<double> soc, bat_cap;  // [A]
   // operand domains of the battery rule's range-test-free variant (battery_rule_r<false>):
@@ -442,9 +446,16 @@ int p2pmg_create(const p2pmg_config* cfg, int device, p2pmg_ctx** out) {
     if (hipMemsetAsync(c->qdelta, 0, p2pmg::kDeltaCopies * c->delta_n() * 8, c->stream) != hipSuccess)
       return bail(P2PMG_E_HIP);
   }
-  if (c->hp_lv.alloc(A) != hipSuccess || c->soc.alloc(A) != hipSuccess || c->thermal.alloc(A) != hipSuccess)
+  if (c->hp_lv.alloc(A) != hipSuccess || c->soc.alloc(A) != hipSuccess || c->thermal.alloc(A) != hipSuccess ||
+      c->learn.alloc(A) != hipSuccess)
     return bail(P2PMG_E_NOMEM);
   {
+    // the config's alpha, gamma and comfort weight for every agent: a context that never calls
+    // p2pmg_set_learning computes what the broadcast kernel arguments did
+    c->h_learn.assign(A, p2pmg::LearnRow{cfg->alpha, cfg->gamma, cfg->penalty_weight, {0.0f, 0.0f, 0.0f}});
+    if (hipMemcpyAsync(c->learn, c->h_learn.data(), A * sizeof(p2pmg::LearnRow), hipMemcpyHostToDevice, c->stream) !=
+        hipSuccess)
+      return bail(P2PMG_E_HIP);
     std::vector<float4> lv(A, make_float4(cfg->hp_levels[0], cfg->hp_levels[1], cfg->hp_levels[2], 0.0f));
     // the config's scalars for every agent: a context that never calls p2pmg_set_thermal computes
     // what the broadcast kernel arguments did
@@ -698,6 +709,8 @@ static EpisodeParams episode_params(p2pmg_ctx* c, const p2pmg_episode_args* args
   p.bat_sqrt_eff = c->bat_sqrt_eff;
   p.hp_lv = c->hp_lv;
   p.thermal = c->thermal;
+  p.learn = c->learn;
+  p.eps_tab = c->eps_table ? c->eps_cur : nullptr;
   p.dummy = c->dummy;
   p.nt = g.n_time_states;
   p.nT = g.n_temp_states;
@@ -797,6 +810,7 @@ static int prepare_fast(p2pmg_ctx* c, const p2pmg_episode_args* args, const Chai
     p2pmg::eps_threshold(eps[0], o.eps_thr, o.eps_all);
     o.n_ep = (int)eps.size();
     o.words_stride = wpe;
+    o.eps_tab = nullptr;
     o.ep_all = 0;
     for (int k = 0; k < o.n_ep; ++k) {
       int all = 0;
@@ -806,6 +820,17 @@ static int prepare_fast(p2pmg_ctx* c, const p2pmg_episode_args* args, const Chai
     return o;
   };
   // this slot's pre-pass: computed by the previous launch if it guessed these arguments
+  if (c->eps_table) {
+    // a per-scenario epsilon table: this launch's own pre-pass from its rows, no speculation, and
+    // neither slot left for a later plain launch to take as a hit
+    p2pmg::PrepOut o = prep_out(ps, args->episode, cur);
+    o.eps_tab = c->eps_cur;
+    HIP_TRY(c, p2pmg::launch_step_prepass(p, o, c->stream));
+    *next = prep_out(ps ^ 1, args->episode + n_ep, nxt_eps);  // unused: the plan does not speculate
+    c->spec_misses++;
+    c->spec_valid[0] = c->spec_valid[1] = false;
+    return P2PMG_OK;
+  }
   const bool hit = c->spec_valid[ps] && c->spec_version[ps] == c->inputs_version &&
                    (!philox || (c->spec_episode[ps] == args->episode && c->spec_chain[ps] == cur));
   if (!hit) HIP_TRY(c, p2pmg::launch_step_prepass(p, prep_out(ps, args->episode, cur), c->stream));
@@ -920,9 +945,45 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
   return P2PMG_OK;
 }
 
+static int run_episodes_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, const double* epsilons, int next_n,
+                             const double* next_epsilons);
+
 int p2pmg_run_episodes(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, const double* epsilons, int next_n,
                        const double* next_epsilons) {
   if (!c || !args || n < 1 || !epsilons || (next_n > 0 && !next_epsilons)) return P2PMG_E_INVALID;
+  return run_episodes_impl(c, args, n, epsilons, next_n, next_epsilons);
+}
+
+int p2pmg_run_episodes_eps(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, const double* eps) {
+  if (!c || !args || n < 1 || !eps) return P2PMG_E_INVALID;
+  if (c->dqn) return fail(c, P2PMG_E_UNSUPPORTED, "run_episodes_eps: tabular contexts only");
+  if (args->mode != P2PMG_MODE_TRAIN || args->rng != P2PMG_RNG_PHILOX)
+    return fail(c, P2PMG_E_INVALID, "run_episodes_eps: Philox training only (replay codes carry each agent's own epsilon)");
+  const size_t S = (size_t)c->S, cells = (size_t)n * S;
+  std::vector<uint2> tab(cells);
+  std::vector<double> first((size_t)n);  // scenario 0's schedule: what the plan's heuristics read
+  for (size_t k = 0; k < cells; ++k) {
+    if (!(std::isfinite(eps[k]) && eps[k] >= 0.0 && eps[k] <= 1.0))
+      return fail(c, P2PMG_E_INVALID, "run_episodes_eps: epsilon outside [0, 1] at entry " + std::to_string(k));
+    int all = 0;
+    p2pmg::eps_threshold(eps[k], tab[k].x, all);
+    tab[k].y = (uint32_t)all;
+  }
+  for (int k = 0; k < n; ++k) first[(size_t)k] = eps[(size_t)k * S];
+  HIP_TRY(c, c->eps_tab.grow(cells));
+  HIP_TRY(c, hipMemcpyAsync(c->eps_tab, tab.data(), cells * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->eps_table = true;
+  c->eps_cur = c->eps_tab;
+  const int rc = run_episodes_impl(c, args, n, first.data(), 0, nullptr);
+  c->eps_table = false;
+  c->eps_cur = nullptr;
+  return rc;
+}
+
+// n episodes at epsilons[k]; with c->eps_table, at the rows of c->eps_tab instead (epsilons: scenario 0's)
+static int run_episodes_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, const double* epsilons, int next_n,
+                             const double* next_epsilons) {
   if (!c->dqn && (!c->have_env || !c->have_prof || !c->have_params))
     return fail(c, P2PMG_E_STATE, "run_episodes: env, profiles and agent params must be set first");
   // at least one full chain's worth, so a caller's chains never reallocate
@@ -936,6 +997,7 @@ int p2pmg_run_episodes(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, cons
       a.epsilon = epsilons[k];
       a.flags = args->flags | P2PMG_FLAG_NEXT_EPSILON;
       a.next_epsilon = k + 1 < n ? epsilons[k + 1] : next_n > 0 ? next_epsilons[0] : epsilons[k];
+      if (c->eps_table) c->eps_cur = c->eps_tab + (size_t)k * c->S;  // this episode's row
       RC_TRY(run_episode_impl(c, &a, nullptr));
       HIP_TRY(c, hipMemcpyAsync(c->chain_rew + (size_t)k * c->S, c->ep_reward,
                                 (size_t)c->S * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
@@ -959,6 +1021,7 @@ int p2pmg_run_episodes(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, cons
     }
     a.episode = args->episode + k0;
     a.epsilon = epsilons[k0];
+    if (c->eps_table) c->eps_cur = c->eps_tab + (size_t)k0 * c->S;  // this part's rows
     RC_TRY(run_episode_impl(c, &a, &req));
   }
   c->chain_n = n;
@@ -1327,6 +1390,41 @@ int p2pmg_get_thermal(p2pmg_ctx* c, float* params) {
   return P2PMG_OK;
 }
 
+int p2pmg_set_learning(p2pmg_ctx* c, const double* alpha, const double* gamma, const float* penalty_weight) {
+  if (!c) return P2PMG_E_INVALID;
+  if (c->dqn) return fail(c, P2PMG_E_UNSUPPORTED, "set_learning: tabular contexts only");
+  const p2pmg_config& g = c->cfg;
+  std::vector<p2pmg::LearnRow> lr((size_t)c->A, p2pmg::LearnRow{g.alpha, g.gamma, g.penalty_weight, {0.0f, 0.0f, 0.0f}});
+  for (size_t a = 0; a < lr.size(); ++a) {  // validated in full before anything changes
+    if (alpha) lr[a].alpha = alpha[a];
+    if (gamma) lr[a].gamma = gamma[a];
+    if (penalty_weight) lr[a].penw = penalty_weight[a];
+    if (!(std::isfinite(lr[a].alpha) && lr[a].alpha >= 0.0 && lr[a].alpha <= 1.0))
+      return fail(c, P2PMG_E_INVALID, "set_learning: alpha outside [0, 1] for agent " + std::to_string(a));
+    if (!(std::isfinite(lr[a].gamma) && lr[a].gamma >= 0.0 && lr[a].gamma <= 1.0))
+      return fail(c, P2PMG_E_INVALID, "set_learning: gamma outside [0, 1] for agent " + std::to_string(a));
+    if (!(std::isfinite(lr[a].penw) && lr[a].penw >= 0.0f))
+      return fail(c, P2PMG_E_INVALID, "set_learning: negative or non-finite penalty weight for agent " + std::to_string(a));
+  }
+  // no kernel's pre-pass reads these, so the speculative slots stay valid
+  HIP_TRY(c, hipMemcpyAsync(c->learn, lr.data(), lr.size() * sizeof(p2pmg::LearnRow), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->h_learn = std::move(lr);
+  c->learning_set = alpha || gamma || penalty_weight;
+  return P2PMG_OK;
+}
+
+int p2pmg_get_learning(p2pmg_ctx* c, double* alpha, double* gamma, float* penalty_weight) {
+  if (!c) return P2PMG_E_INVALID;
+  if (c->dqn) return fail(c, P2PMG_E_UNSUPPORTED, "get_learning: tabular contexts only");
+  for (size_t a = 0; a < c->h_learn.size(); ++a) {
+    if (alpha) alpha[a] = c->h_learn[a].alpha;
+    if (gamma) gamma[a] = c->h_learn[a].gamma;
+    if (penalty_weight) penalty_weight[a] = c->h_learn[a].penw;
+  }
+  return P2PMG_OK;
+}
+
 int p2pmg_set_battery(p2pmg_ctx* c, const double* capacity, double min_soc, double max_soc, double efficiency,
                       const double* soc0) {
   if (!c) return P2PMG_E_INVALID;
@@ -1573,7 +1671,7 @@ int p2pmg_q_calls(p2pmg_ctx* c, int n, const int32_t* agents, const float* s_obs
                        reinterpret_cast<const float*>(d + off_r), reinterpret_cast<const float*>(d + off_ns),
                        reinterpret_cast<int32_t*>(d + off_act), reinterpret_cast<double*>(d + off_q), c->q,
                        (uint32_t)c->n_states, g.n_time_states, g.n_temp_states, g.n_balance_states, g.n_p2p_states,
-                       g.alpha, g.gamma};
+                       c->learn};
   if (e == hipSuccess) e = p2pmg::launch_q_calls(p, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(actions_out, d + off_act, 4 * nb, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(q_out, d + off_q, 8 * nb, hipMemcpyDeviceToHost, c->stream);

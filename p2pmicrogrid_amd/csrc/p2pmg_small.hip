@@ -56,11 +56,12 @@ __global__ void philox_codes_kernel(const EpisodeParams p, uint32_t* __restrict_
   const int t = (int)(k / p.A), a = (int)(k % p.A);
   const int R1 = p.R + 1, W = (R1 + 3) >> 2;
   const uint32_t gid = p.agent_offset + (uint32_t)a;
-  const uint64_t codes = philox_codes_of(p, t, gid);
+  const EpsThr e = eps_of(p, a / p.N);  // the scenario's own threshold under p2pmg_run_episodes_eps
+  const uint64_t codes = philox_codes_of(p, t, gid, e);
   for (int w = 0; w < W; ++w)
     words[((size_t)t * W + w) * p.A + a] =
         w < 2 ? (uint32_t)(codes >> (32 * w))
-              : philox_code_word(t, R1, w, (uint32_t)p.episode, gid, p.eps_thr, p.eps_all, p.seed_lo, p.seed_hi);
+              : philox_code_word(t, R1, w, (uint32_t)p.episode, gid, e.thr, e.all, p.seed_lo, p.seed_hi);
 }
 
 // host replay codes u8 [T][R1][A] -> code words [T][W][A]
@@ -386,7 +387,8 @@ __global__ void q_calls_kernel(const QCallParams p) {
       const uint32_t nrow = (uint32_t)(((idx_time(n[0], p.nt) * p.nT + idx_temp(n[1], p.nT)) * p.nb +
                                         idx_plain(n[2], p.nb)) * p.np + idx_plain(n[3], p.np));
       const QT qmax = max3(load_row(q + nrow * kQPad));
-      q[srow * kQPad + a] = td_update(q[srow * kQPad + a], p.rewards[k], qmax, p.alpha, p.gamma);
+      const LearnRow lr = p.learn[p.agents[k]];  // the agent's own alpha and gamma (rl.py:125-128)
+      q[srow * kQPad + a] = td_update(q[srow * kQPad + a], p.rewards[k], qmax, lr.alpha, lr.gamma);
     }
   }
 }

@@ -251,14 +251,16 @@ struct KC {
 // {setpoint, lower, upper, cop}, one 16-B load per lane in the kernel's prologue.  The load is
 // unconditional (masked-off lanes read agent 0's entry, as for hp_lv), so its wait is not tied to a
 // branch; the four values are per-lane VGPRs from then on, where the broadcast arguments were pinned.
-__device__ __forceinline__ KC pin_constants(const EpisodeParams& p, const float4 th) {
+// The learner's alpha, gamma and comfort weight (QActor rl.py:58-71, agent.py:225-232) are the
+// agent's own in the same way: lr = learn[a], loaded beside thermal[a].
+__device__ __forceinline__ KC pin_constants(const EpisodeParams& p, const float4 th, const LearnRow lr) {
   KC k;
   k.setpoint = th.x; k.margin = vpin(p.margin); k.lower = th.y; k.upper = th.z;
   k.inv_ci = vpin(p.inv_ci); k.inv_cm = vpin(p.inv_cm); k.inv_ri = vpin(p.inv_ri); k.inv_re = vpin(p.inv_re);
   k.inv_rvent = vpin(p.inv_rvent); k.c_in = vpin(p.c_in); k.c_m = vpin(p.c_m); k.solar = vpin(p.solar);
   k.cop = th.w; k.spm = vpin(p.spm); k.slot = vpin(p.slot); k.mph = vpin(p.mph); k.kilo = vpin(p.kilo);
-  k.penw = vpin(p.penw);
-  k.alpha = vpin(p.alpha); k.gamma = vpin(p.gamma);
+  k.penw = lr.penw;
+  k.alpha = lr.alpha; k.gamma = lr.gamma;
   k.nt = vpin(p.nt); k.nT = vpin(p.nT); k.nb = vpin(p.nb); k.np = vpin(p.np);
   return k;
 }
@@ -317,8 +319,26 @@ __device__ __forceinline__ StepIdx make_step(const KC& p, const Dims<B20>& D, bo
 // Philox exploration codes of every round of step t (p2pmg_device.h::philox_step_codes, layout
 // oracle/philox.py::decision_draws): byte r = code of round r, 255 = greedy (QActor.select_action
 // rl.py:100-111)
+// The explore threshold of a lane's scenario: the launch's scalars, or row `row`, scenario s of the
+// per-scenario table (p2pmg_run_episodes_eps).  {thr, all} as eps_threshold forms them.
+struct EpsThr {
+  uint32_t thr;
+  int all;
+};
+__device__ __forceinline__ EpsThr eps_of(const EpisodeParams& p, int s, int row = 0) {
+  EpsThr e{p.eps_thr, p.eps_all};
+  if (p.eps_tab) {
+    const uint2 v = p.eps_tab[(size_t)row * p.S + s];
+    e.thr = v.x;
+    e.all = (int)v.y;
+  }
+  return e;
+}
+__device__ __forceinline__ uint64_t philox_codes_of(const EpisodeParams& p, int t, uint32_t gid, const EpsThr& e) {
+  return philox_step_codes(t, p.R + 1, (uint32_t)p.episode, gid, e.thr, e.all, p.seed_lo, p.seed_hi);
+}
 __device__ __forceinline__ uint64_t philox_codes_of(const EpisodeParams& p, int t, uint32_t gid) {
-  return philox_step_codes(t, p.R + 1, (uint32_t)p.episode, gid, p.eps_thr, p.eps_all, p.seed_lo, p.seed_hi);
+  return philox_codes_of(p, t, gid, EpsThr{p.eps_thr, p.eps_all});
 }
 
 // all rounds' codes of step t packed one byte per round (round r in bits 8r..8r+7)
@@ -330,14 +350,18 @@ struct CodeWords {
   uint64_t gen;     // in-kernel Philox word (p.rng == 1)
 };
 __device__ __forceinline__ CodeWords step_codes(const EpisodeParams& p, const uint32_t* codes_a, size_t off, int t,
-                                                int a, int W, bool gen = true) {
+                                                int a, int W, const EpsThr& e, bool gen = true) {
   // code words [T][W][A] (replay upload or Philox pre-pass); off = t * W * A
   CodeWords c;
   c.w0 = codes_a[off];
   c.w1 = codes_a[W > 1 ? off + (size_t)p.A : off];
   c.gen = ~0ull;
-  if (gen && p.rng == 1) c.gen = philox_codes_of(p, t, p.agent_offset + (uint32_t)a);
+  if (gen && p.rng == 1) c.gen = philox_codes_of(p, t, p.agent_offset + (uint32_t)a, e);
   return c;
+}
+__device__ __forceinline__ CodeWords step_codes(const EpisodeParams& p, const uint32_t* codes_a, size_t off, int t,
+                                                int a, int W, bool gen = true) {
+  return step_codes(p, codes_a, off, t, a, W, EpsThr{p.eps_thr, p.eps_all}, gen);
 }
 __device__ __forceinline__ uint64_t code_word(const EpisodeParams& p, const CodeWords& c, bool active) {
   const int R1 = p.R + 1;

@@ -208,6 +208,30 @@ class DeviceCommunityBatch:
         self._chk(self.L.p2pmg_get_thermal(self._ctx, out), "get_thermal")
         return out.reshape(self.S, self.N, 4)
 
+    def set_learning(self, alpha=None, gamma=None, penalty_weight=None):
+        """Per-agent learner constants: each QActor's own alpha and gamma (rl.py:58-71) and the comfort
+        weight of the agent's reward (agent.py:225-232).  Scalars or anything that broadcasts to
+        [S, N]; None keeps the config's value for that field, and set_learning() restores the
+        config's values for every agent."""
+        def per_agent(x, dt):
+            if x is None:
+                return None
+            x = np.asarray(x, dt)
+            try:
+                return np.ascontiguousarray(np.broadcast_to(x, (self.S, self.N)).reshape(self.A))
+            except ValueError:
+                raise ValueError(f"learning arrays must broadcast to [{self.S}, {self.N}], got {x.shape}") from None
+        a, g, w = per_agent(alpha, np.float64), per_agent(gamma, np.float64), per_agent(penalty_weight, F32)
+        self._chk(self.L.p2pmg_set_learning(self._ctx, *(None if x is None else x.ctypes.data for x in (a, g, w))),
+                  "set_learning")
+
+    def get_learning(self) -> Dict[str, np.ndarray]:
+        """{"alpha": [S, N] f64, "gamma": [S, N] f64, "penalty_weight": [S, N] f32} the kernels read."""
+        a, g, w = np.empty(self.A, np.float64), np.empty(self.A, np.float64), np.empty(self.A, F32)
+        self._chk(self.L.p2pmg_get_learning(self._ctx, a.ctypes.data, g.ctypes.data, w.ctypes.data), "get_learning")
+        shape = (self.S, self.N)
+        return {"alpha": a.reshape(shape), "gamma": g.reshape(shape), "penalty_weight": w.reshape(shape)}
+
     def set_battery(self, capacity=None, min_soc=0.1, max_soc=0.9, efficiency=0.9, soc0=None):
         """Battery per agent (capacity [S, N] in J, 0 = none); None disables storage."""
         if capacity is None:
@@ -284,7 +308,7 @@ class DeviceCommunityBatch:
         return out
 
     # ----------------------------------------------------------------- the hot path
-    def run_episode(self, mode: str = "train", rng: str = "replay", episode: int = 0, epsilon: float = 0.81,
+    def run_episode(self, mode: str = "train", rng: str = "replay", episode: int = 0, epsilon=0.81,
                     record: Sequence[str] = (), philox: str = "auto", kernel: str = "auto",
                     scen_per_wave: int = 0, reset_sigma: Optional[float] = None,
                     next_epsilon: Optional[float] = None):
@@ -297,7 +321,17 @@ class DeviceCommunityBatch:
         reset_temperatures_philox(episode + 1, reset_sigma), fused into the episode launch.
         next_epsilon: the next episode's epsilon when the caller knows its decay schedule
         (community.py:279-286), so that the speculative pre-pass this launch writes for
-        episode + 1 is a hit (None: the same epsilon)."""
+        episode + 1 is a hit (None: the same epsilon).
+        epsilon: a float, or [S] for one epsilon per scenario (Philox training only; the launch is
+        then run_episodes(episode, epsilon[None, :]), without a speculative pre-pass)."""
+        if np.ndim(epsilon) != 0:
+            eps = np.asarray(epsilon, np.float64)
+            if eps.shape != (self.S,):
+                raise ValueError(f"epsilon must be a float or [{self.S}], got {eps.shape}")
+            if mode != "train" or rng != "philox":
+                raise ValueError("per-scenario epsilon needs mode='train' and rng='philox'")
+            return self.run_episodes(episode, eps[None, :], reset_sigma=reset_sigma, scen_per_wave=scen_per_wave,
+                                     record=record, philox=philox, kernel=kernel)
         mask = 0
         for r in record:
             mask |= _lib.REC[r]
@@ -315,18 +349,34 @@ class DeviceCommunityBatch:
         self._recorded = mask
 
     def run_episodes(self, episode: int, epsilons, reset_sigma: Optional[float] = None,
-                     next_epsilons=None, scen_per_wave: int = 0, record: Sequence[str] = ()):
+                     next_epsilons=None, scen_per_wave: int = 0, record: Sequence[str] = (), philox: str = "auto",
+                     kernel: str = "auto"):
         """Train len(epsilons) consecutive episodes with Philox draws (community.py:279-286's loop
         body): episode + k at epsilons[k], each ending with the T0 reset when reset_sigma is given.
         Where the fast kernel applies, chained launches run up to 64 episodes each, every wave
         going through its episodes back to back; results are those of run_episode per episode,
         bit for bit.  next_epsilons: the next call's epsilons (its speculative pre-pass).  record:
-        what the last episode leaves in the record buffers (as after run_episode per episode)."""
-        eps = np.ascontiguousarray(epsilons, dtype=np.float64).reshape(-1)
+        what the last episode leaves in the record buffers (as after run_episode per episode).
+        epsilons [n, S]: scenario s explores at epsilons[k, s] in episode + k (p2pmg_run_episodes_eps;
+        next_epsilons is ignored: the call does not speculate).  philox / kernel: as in run_episode."""
+        eps = np.ascontiguousarray(epsilons, dtype=np.float64)
+        if eps.ndim > 2 or (eps.ndim == 2 and eps.shape[1] != self.S) or eps.size == 0:
+            raise ValueError(f"epsilons must be [n] or [n, {self.S}], got {eps.shape}")
         flags = _lib.FLAG_RESET_T0 if reset_sigma is not None else 0
+        flags |= {"auto": 0, "prepass": _lib.FLAG_PHILOX_PREPASS, "inkernel": _lib.FLAG_PHILOX_INKERNEL}[philox]
+        flags |= {"auto": 0, "general": _lib.FLAG_GENERAL_KERNEL, "tile": _lib.FLAG_TILE_KERNEL}[kernel]
         mask = 0
         for r in record:
             mask |= _lib.REC[r]
+        if eps.ndim == 2:
+            args = _lib.EpisodeArgs(_lib.MODE_TRAIN, _lib.RNG_PHILOX, int(episode), mask, 0.0, flags,
+                                    int(scen_per_wave), float(reset_sigma or 0.0), 0.0)
+            self._chk(self.L.p2pmg_run_episodes_eps(self._ctx, C.byref(args), int(eps.shape[0]), eps),
+                      "run_episodes_eps")
+            self._recorded = mask
+            self._chain_len = int(eps.shape[0])
+            return
+        eps = eps.reshape(-1)
         args = _lib.EpisodeArgs(_lib.MODE_TRAIN, _lib.RNG_PHILOX, int(episode), mask, float(eps[0]), flags,
                                 int(scen_per_wave), float(reset_sigma or 0.0), 0.0)
         nxt = None if next_epsilons is None else np.ascontiguousarray(next_epsilons, dtype=np.float64).reshape(-1)

@@ -69,13 +69,19 @@ class QActor(ActorInterface):
     # ------------------------------------------------------------ device binding
     def bind(self, engine, slot: int) -> None:
         """Attach to agent ``slot`` of a DeviceCommunityBatch (uploads any pending table)."""
-        if (engine.cfg.alpha, engine.cfg.gamma) != (self._alpha, self._gamma):
-            raise ValueError("QActor alpha/gamma differ from the device context's")
         if engine.q_shape != self._shape:
             raise ValueError(f"QActor table shape {self._shape} != device {engine.q_shape}")
         table = self._host_table if self._engine is None else self.q_table
         self._engine, self._slot = engine, slot
         self._host_table = None
+        # this actor's own alpha and gamma (rl.py:58-71) into its slot of the engine's per-agent arrays
+        # (a slot is an agent where every agent has its table; shared tables keep the engine's values)
+        if engine.n_tables == engine.A:
+            cur = engine.get_learning()
+            a, g = cur["alpha"].reshape(-1), cur["gamma"].reshape(-1)
+            if (a[slot], g[slot]) != (self._alpha, self._gamma):
+                a[slot], g[slot] = self._alpha, self._gamma
+                engine.set_learning(alpha=a, gamma=g, penalty_weight=cur["penalty_weight"])
         if table is not None:
             engine.set_q(np.asarray(table)[None], first=slot)
 
