@@ -59,8 +59,12 @@ __device__ __forceinline__ void gather_even(float ev, float (&col)[N], int i) {
 // prologue under a divergent branch.  What was wave-uniform per episode (step offsets, code-word
 // base) is per lane.  The one access whose serial order cannot be kept, step T - 1's next-state
 // row (key of step 0, which the follower episode has been writing since its own step 0), is served
-// from a snapshot of max3 of those rows that the follower takes in its prologue (LDS, one slot per
-// half, read by the other half L steps later).
+// from the follower's undo log: the first time the follower stores into a row (key of step 0,
+// temperature bin, p2p = 0) it leaves max3 of the row as it read it in LDS (one slot per half and
+// bin, one bit per bin in a per-lane mask), and the leader's step T - 1 takes that value where the
+// bit is set and its own loaded row where it is clear.  The hazard rule puts every such store at least
+// four steps before the leader loads the row, and every leader store to those rows before the
+// follower's first read, so the logged value is what the serial chain reads.
 template <int N, typename QT, int R1, bool TRAIN, int BAT, bool NARROW, bool PIPE = false>
 __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams p, const uint2* __restrict__ pre,
                                                              FastRec* __restrict__ recs, int spw, int n_cons,
@@ -166,12 +170,19 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
   // halves of the wave are L steps apart, so all of it is per lane there.
   bool st_on = active;           // the lane stores (PIPE: and its half has an episode running)
   size_t rec_adv = rec_step;     // record pointer advance per step
-  bool wrap_l = false;           // PIPE: this lane's step T - 1 takes max3 of the next-state row from the snapshot
+  bool wrap_l = false;           // PIPE: this lane's step T - 1 takes max3 of the next-state row from the follower's log
   bool wrap_it = false;          // PIPE: the loop's last iteration of a phase (uniform)
-  QT* snap = nullptr;            // PIPE: [2][32 temperature bins][32 lanes] max3 of the rows (key of step 0, bin, p2p = 0)
+  // PIPE: the undo log of the rows (key of step 0, temperature bin, p2p = 0) this lane's episode has
+  // stored into: max3 of each row as first read, [2 halves][32 bins][32 lanes] and a dummy slot per lane
+  // (a step that logs nothing writes there: the LDS store is unconditional); bit iT of wlog_m = logged
+  QT* wlog = nullptr;
+  uint32_t* wlog_mask = nullptr;  // [64 lanes] every lane's wlog_m, for the other half's step T - 1
+  uint32_t wlog_m = 0u, key0 = 0u;
   if constexpr (PIPE) {
-    __shared__ QT snap_lds[2 * 32 * 32];
-    snap = snap_lds;
+    __shared__ QT wlog_lds[2 * 32 * 32 + kWave];
+    __shared__ uint32_t wlog_mask_lds[kWave];
+    wlog = wlog_lds;
+    wlog_mask = wlog_mask_lds;
   }
   const uint32_t* codes_a;
   char* rec_ptr;
@@ -254,33 +265,17 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
         t0_draw(p.seed_lo, p.seed_hi, p.episode + ep + 1, p.agent_offset + (uint32_t)a, k.setpoint, p.reset_sigma, t0_in,
                 t0_m);
     } else {
-      // The snapshot for the other half's step T - 1: max3 of this agent's rows (key of step 0, every
-      // temperature bin, p2p = 0) as they are before this episode's first TD store.  The other half's
-      // stores to that key are at least four steps past (the hazard rule), so these are the values
-      // its serial step T - 1 would read.  Loaded kSnap rows at a time, the first batch under the T0 draw.
-      constexpr int kSnap = 10;
-      const uint32_t key0 = pS[0].y & 0xFFFFu;
-      const int nTi = p.nT;
-      Row4<QT> sr[kSnap];
-      auto snap_load = [&](int it0) {
-#pragma unroll
-        for (int j = 0; j < kSnap; ++j) sr[j] = gat(strip_of(key0, it0 + j < nTi ? it0 + j : nTi - 1) + (uint32_t)ip_zero);
-      };
-      auto snap_store = [&](int it0) {
-#pragma unroll
-        for (int j = 0; j < kSnap; ++j)
-          if (it0 + j < nTi) snap[(grp * 32 + it0 + j) * 32 + hl] = max3(sr[j]);
-      };
-      snap_load(0);
-      // the T0 this half's NEXT episode (ep + 2) starts from, or the one the chain leaves behind
+      // this episode's undo log starts empty (read by the other half L steps later, at its step T - 1)
+      key0 = pS[0].y & 0xFFFFu;
+      wlog_m = 0u;
+      wlog_mask[lane] = 0u;
+      // the T0 this half's NEXT episode (ep + 2) starts from, or the one the chain leaves behind: drawn
+      // while the first rows are in flight
+#if P2PMG_ABLATE != 13  // 13 (timing-only): no draw at the phase boundary (what moving it off the wave could save)
       if (active)
         t0_draw(p.seed_lo, p.seed_hi, p.episode + (ep + 2 < n_chain ? ep + 2 : n_chain), p.agent_offset + (uint32_t)a,
                 k.setpoint, p.reset_sigma, t0_in, t0_m);
-      snap_store(0);
-      for (int it0 = kSnap; it0 < nTi; it0 += kSnap) {
-        snap_load(it0);
-        snap_store(it0);
-      }
+#endif
     }
   };
   // the end of an episode (non-PIPE)
@@ -594,14 +589,24 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
       QT qmax = max3(patched(rowN, aN, pprev));
       if constexpr (PIPE && P == 2) {
         // step T - 1 of an episode with a follower: its next-state row (key of step 0) has been
-        // written by the follower since its own step 0; the follower's snapshot holds what the
-        // serial chain reads here (the row's load above is still issued: the waits stay static)
+        // written by the follower since its own step 0, every such store issued before the row's load;
+        // where the follower logged the row, the log holds what the serial chain reads here
         if (wrap_it) {
-          const QT sv = snap[((grp ^ 1) * 32 + iT) * 32 + hl];
+          const QT sv = wlog[((grp ^ 1) * 32 + iT) * 32 + hl];
+          const uint32_t fm = wlog_mask[lane ^ 32];
 #if P2PMG_ABLATE != 12  // 12 (test-only): the loaded row, which the follower has overwritten; the dense-collision test must then fail
-          qmax = wrap_l ? sv : qmax;
+          qmax = wrap_l && ((fm >> iT) & 1u) != 0u ? sv : qmax;
 #endif
         }
+      }
+      if constexpr (PIPE) {
+        // the first store of this episode into a row the leader's step T - 1 may read: log max3 of the
+        // row as this step read it (rowR holds the lane's own previous store).  The hazard rule keeps
+        // such steps out of an episode's second half.
+        const bool first = st_on && (p0.y & 0xFFFFu) == key0 && ip == ip_zero && ((wlog_m >> iT) & 1u) == 0u;
+        wlog[first ? (grp * 32 + iT) * 32 + hl : 2 * 32 * 32 + lane] = max3(rowR);
+        wlog_m |= first ? 1u << iT : 0u;
+        wlog_mask[lane] = wlog_m;
       }
       const QT qnew = td_update(qsa, rw, qmax, k.alpha, k.gamma);
       *((PIPE ? st_on : active) ? q + srow * kQPad + act : q_dummy) = qnew;

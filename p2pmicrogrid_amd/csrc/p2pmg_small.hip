@@ -91,8 +91,8 @@ __global__ void step_prepass_kernel(const EpisodeParams p, const PrepOut o) {
 // step u of an agent's earlier episode and step v of its later one conflict when they touch rows of
 // one (time bin, balance bin) key with a write involved: lo(u) == lo(v) (the step's own rows, read
 // and written), lo(u) == hi(v) or hi(u) == lo(v) (hi: the next-state row, read only).  Step T - 1's
-// next-state read alone does not count: the kernel serves it from a snapshot.  *out = max u - v over
-// every agent's conflicting pairs (atomicMax; the caller presets it to 0, what u == v gives).
+// next-state read alone does not count: the kernel serves it from the follower's undo log.  *out =
+// max u - v over every agent's conflicting pairs (atomicMax; the caller presets it to 0, what u == v gives).
 // One thread per agent, O(T^2) compares, the words read through the caches.
 __global__ void chain_lag_kernel(int T, int A, const uint2* __restrict__ pre, int* __restrict__ out) {
   const int a = (int)(blockIdx.x * blockDim.x + threadIdx.x);
