@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag, p2pmg_set_learning, p2pmg_get_learning, p2pmg_run_episodes_eps) */
+#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag, p2pmg_set_learning, p2pmg_get_learning, p2pmg_run_episodes_eps, p2pmg_table_stats, p2pmg_greedy_policy, p2pmg_policy_mark, p2pmg_policy_changes, n_actions = 2 table-only contexts) */
 
 typedef struct p2pmg_ctx p2pmg_ctx;
 
@@ -85,7 +85,8 @@ typedef struct p2pmg_config {
   int32_t n_temp_states;    /* 20 */
   int32_t n_balance_states; /* 20 */
   int32_t n_p2p_states;     /* 20 */
-  int32_t n_actions;        /* 3 (<= 4) */
+  int32_t n_actions;        /* 3; 2: a tabular context that holds tables (set_q, get_q, the table digests) but
+                               runs no episode and no p2pmg_q_calls (P2PMG_E_UNSUPPORTED) */
   double alpha;             /* 1e-5 (rl.py:60); per agent: p2pmg_set_learning */
   double gamma;             /* 0.9  (rl.py:59); per agent: p2pmg_set_learning */
   float hp_levels[4];       /* f32(level * max_power) = {0, 1500, 3000} W (agent.py:268, heating.py:124) */
@@ -206,6 +207,61 @@ int p2pmg_set_replay_codes(p2pmg_ctx* ctx, const uint8_t* codes);            /* 
 int p2pmg_zero_q(p2pmg_ctx* ctx);
 int p2pmg_set_q(p2pmg_ctx* ctx, int first_agent, int count, const void* host, int host_dtype);
 int p2pmg_get_q(p2pmg_ctx* ctx, int first_agent, int count, void* host, int host_dtype);
+
+/* Table digests: what a sweep asks of its learned tables, computed ON THE DEVICE by one streaming pass
+ * over the tables where they lie, so that 8 doubles per table, one byte per state or two counts per
+ * table reach the host instead of the tables (5.1 MB each in f64 at 20^4 states).
+ *
+ * All four calls address tables 0 .. n_tables-1 as p2pmg_get_q does (A per-agent tables, 1 shared table
+ * or N role tables), are stream-ordered after earlier launches and synchronise before returning.  They
+ * read the tables as they are at the call: the pending int64 delta of a shared or role context is NOT
+ * applied (p2pmg_apply_q_delta first, if wanted).  DQN context: P2PMG_E_STATE (no Q-table).
+ * first < 0, count < 0, first + count > n_tables or a NULL output (where not marked optional):
+ * P2PMG_E_INVALID.  count == 0: P2PMG_OK, nothing written.
+ *
+ * Definitions.  A table has n_states ROWS, one per state, in the reference's (time, temp, balance, p2p)
+ * order, time slowest: the order of p2pmg_get_q.  A row's ENTRIES are its n_actions Q-values (the first
+ * n_actions of the 4 stored; the padding is never read into any result).
+ *   visited        a row is visited iff any entry != 0.0.  -0.0 == 0.0, so a row of +-0.0 only is not.
+ *   greedy action  g = 0; for k = 1 .. n_actions-1 in order: if entry[k] > entry[g] then g = k.  The
+ *                  FIRST maximum: the strict-> scan of the episode kernels (QActor.greedy_action,
+ *                  rl.py:113-117).  An unvisited row's greedy action is therefore 0.
+ *   Tables are assumed NaN-free; with NaN entries the results are whatever these comparisons give.
+ * Every result is a count, a minimum or a maximum: none depends on any order of evaluation, and "equal"
+ * below means bit for bit.  f32 tables widen to f64 exactly.
+ *
+ * p2pmg_table_stats: P2PMG_TABLE_STATS f64 values per table, stats[k][.] for table first + k:
+ *    0 visited     number of visited rows
+ *    1 q_min       minimum over all n_states x n_actions entries
+ *    2 q_max       maximum over the same entries
+ *    3 abs_max     maximum of |entry| over the same entries (= max(-q_min, q_max)): the normaliser of the
+ *                  reference's plots, np.abs(q_table).max() (data_analysis.py plot_q_values_com / _no_com)
+ *    4..7 greedy[a]  number of VISITED rows whose greedy action is a; 0 for a >= n_actions
+ *                  (fields 4..7 sum to field 0)
+ * Counts are exact in f64.  A zero value of fields 1-3 is returned as +0.0, whatever the signs of the
+ * zeros in the table. */
+#define P2PMG_TABLE_STATS 8
+int p2pmg_table_stats(p2pmg_ctx* ctx, int first, int count, double* stats /* [count][P2PMG_TABLE_STATS] */);
+/* The packed greedy policy: one byte per row, the row's greedy action (0 .. n_actions-1) if the row is
+ * visited, else P2PMG_POLICY_UNVISITED.  1/32 of an f64 table (1/16 of an f32 one). */
+#define P2PMG_POLICY_UNVISITED 255
+int p2pmg_greedy_policy(p2pmg_ctx* ctx, int first, int count, uint8_t* policy /* [count][n_states] */);
+/* Policy churn.  p2pmg_policy_mark stores the packed policy (as p2pmg_greedy_policy defines it) of EVERY
+ * table in a snapshot [n_tables][n_states] u8 that the context owns on the device; it is allocated by
+ * the first call (P2PMG_E_NOMEM if that fails, and there is then no snapshot).  p2pmg_set_q and
+ * p2pmg_zero_q do not touch the snapshot.
+ * p2pmg_policy_changes compares the tables as they are now with the snapshot, per table first + k:
+ *    changed[k]        number of rows whose greedy action differs from the snapshot's, where a snapshot
+ *                      byte 255 stands for action 0 (an unvisited row's greedy action) and the current
+ *                      side is the greedy action whether or not the row is visited
+ *    newly_visited[k]  number of rows whose snapshot byte is 255 and that are visited now
+ *                      (newly_visited may be NULL)
+ * remark != 0: the same pass overwrites the snapshot of tables [first, first + count), and of no other,
+ * with the current packed policy; each table is read once.  Before the first p2pmg_policy_mark:
+ * P2PMG_E_STATE. */
+int p2pmg_policy_mark(p2pmg_ctx* ctx);
+int p2pmg_policy_changes(p2pmg_ctx* ctx, int first, int count, int64_t* changed /* [count] */,
+                         int64_t* newly_visited /* [count] or NULL */, int remark);
 
 /* the hot path */
 int p2pmg_run_episode(p2pmg_ctx* ctx, const p2pmg_episode_args* args);

@@ -37,6 +37,7 @@ UNITS = [
     *[("p2pmg_general.hip", f"P2PMG_GENERAL_SLICE={k}", [], f"general_{k}.o") for k in range(9)],
     ("p2pmg_dqn.hip", None, [], "p2pmg_dqn.o"),
     ("p2pmg_summary.hip", None, [], "p2pmg_summary.o"),
+    ("p2pmg_tables.hip", None, [], "p2pmg_tables.o"),
     ("p2pmg_runtime.cpp", None, [], "p2pmg_runtime.o"),
     ("p2pmg_plan.cpp", None, [], "p2pmg_plan.o"),
 ]

@@ -24,6 +24,8 @@ DQN_PARAMS = 4609
 RNG_REPLAY, RNG_PHILOX = 0, 1
 REC = {"reward": 1, "cost": 2, "grid": 4, "p2p": 8, "t_in": 16, "action": 32, "index": 64, "loss": 128}
 GREEDY = 255
+TABLE_STATS = 8          # P2PMG_TABLE_STATS
+POLICY_UNVISITED = 255   # P2PMG_POLICY_UNVISITED
 
 EXPORTS = [
     "p2pmg_abi_version", "p2pmg_config_default", "p2pmg_create", "p2pmg_destroy", "p2pmg_last_error", "p2pmg_last_kernel",
@@ -45,6 +47,7 @@ EXPORTS = [
     "p2pmg_set_thermal", "p2pmg_get_thermal", "p2pmg_rc_step_ex", "p2pmg_get_hp_levels",
     "p2pmg_episode_summary",
     "p2pmg_set_learning", "p2pmg_get_learning", "p2pmg_run_episodes_eps",
+    "p2pmg_table_stats", "p2pmg_greedy_policy", "p2pmg_policy_mark", "p2pmg_policy_changes",
 ]
 
 
@@ -117,6 +120,10 @@ def _declare(lib):
         "p2pmg_zero_q": ([vp], i32),
         "p2pmg_set_q": ([vp, i32, i32, vp, i32], i32),
         "p2pmg_get_q": ([vp, i32, i32, vp, i32], i32),
+        "p2pmg_table_stats": ([vp, i32, i32, vp], i32),            # [count][TABLE_STATS] f64
+        "p2pmg_greedy_policy": ([vp, i32, i32, vp], i32),          # [count][n_states] u8
+        "p2pmg_policy_mark": ([vp], i32),
+        "p2pmg_policy_changes": ([vp, i32, i32, vp, vp, i32], i32),  # changed, newly_visited [count] i64
         "p2pmg_run_episode": ([vp, C.POINTER(EpisodeArgs)], i32),
         "p2pmg_run_episodes": ([vp, C.POINTER(EpisodeArgs), i32, dp, i32, vp], i32),
         "p2pmg_run_episodes_eps": ([vp, C.POINTER(EpisodeArgs), i32, dp], i32),  # eps [n][S] f64

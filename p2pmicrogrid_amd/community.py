@@ -266,6 +266,17 @@ class CommunityMicrogrid:
             raise RuntimeError("summary() describes the last run(): call run() first")
         return {k: v[0] for k, v in self._engine.episode_summary(kwh=kwh)["agent"].items()}
 
+    def table_stats(self) -> Dict[str, np.ndarray]:
+        """Per agent: how much of its Q-table is written, its value range and its greedy-action histogram,
+        {"visited", "q_min", "q_max", "abs_max": [N], "greedy": [N, n_actions]} (QActor.table_stats;
+        one device pass over the community's tables once they are on the device)."""
+        if self._dqn or self._rule:
+            raise RuntimeError("table_stats(): only tabular (QActor) communities have Q-tables")
+        if self._engine is not None and all(a.actor._engine is self._engine for a in self.agents):
+            return self._engine.table_stats(0, len(self.agents))
+        per = [a.actor.table_stats() for a in self.agents]
+        return {k: np.stack([np.asarray(p[k]) for p in per]) for k in per[0]}
+
     def run_days(self, days, summary: bool = False) -> List[Dict[str, np.ndarray]]:
         """run() of this community over several days in ONE greedy launch: a per-role-table engine
         (``shared_q="role"``) with one scenario per day, holding one copy of every agent's table

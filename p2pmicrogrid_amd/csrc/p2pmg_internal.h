@@ -1,5 +1,5 @@
 // Internal declarations shared by the kernel units (device code + launchers: p2pmg_general.hip,
-// p2pmg_fast.hip, p2pmg_sq16.hip, p2pmg_small.hip, p2pmg_dqn.hip, p2pmg_summary.hip) and
+// p2pmg_fast.hip, p2pmg_sq16.hip, p2pmg_small.hip, p2pmg_dqn.hip, p2pmg_summary.hip, p2pmg_tables.hip) and
 // p2pmg_runtime.cpp (context, C ABI).  Not part of the public ABI (include/p2pmg.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -264,6 +264,26 @@ struct SummaryParams {
 };
 // summary_agent_kernel then summary_scenario_kernel (which reads agent_out) on the stream
 hipError_t launch_episode_summary(const SummaryParams& p, hipStream_t stream);
+// the table digests (p2pmg_tables.hip): p2pmg_table_stats, p2pmg_greedy_policy, p2pmg_policy_mark and
+// p2pmg_policy_changes are one pass over `count` padded tables with different outputs switched on
+constexpr int kTableStats = 8;  // P2PMG_TABLE_STATS
+struct TableDigestParams {
+  const void* q;         // the first table of the range: [count][n_states][kQPad] f64 | f32
+  size_t n_states;
+  int n_actions, count;
+  unsigned bpt;          // blocks per table (table_digest_blocks): a block never spans tables
+  int dword;             // 1: policy / snapshot bytes move as dwords (n_states % 4 == 0, 4-byte aligned bases)
+  int remark;            // compare: overwrite the snapshot with the current policy in the same pass
+  uint8_t* policy;       // [count][n_states] out, or null
+  uint8_t* snap;         // compare: [count][n_states] snapshot of the same tables
+  double* stat_part;     // stats: [count][bpt][kTableStats] block partials (null: no stats)
+  double* stat_out;      // stats: [count][kTableStats]
+  long long* chg_part;   // compare: [count][bpt][2] {changed, newly visited} (null: no compare)
+  long long* chg_out;    // compare: [count][2]
+};
+unsigned table_digest_blocks(int count, size_t n_states);
+// stats and compare exclude each other; the fold launch follows the pass on the stream
+hipError_t launch_table_digest(const TableDigestParams& p, int q_dtype, hipStream_t stream);
 hipError_t launch_apply_delta(void* q, long long* qdelta, size_t n, int q_dtype, hipStream_t stream);
 hipError_t launch_fold_delta(long long* qdelta, size_t n, hipStream_t stream);
 hipError_t launch_battery_seq(int agents, int steps, const double* bal, double* out_bal, double* soc_hist,

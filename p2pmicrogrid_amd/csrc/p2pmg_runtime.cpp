@@ -161,6 +161,11 @@ struct p2pmg_ctx : p2pmg::PlanFacts {
   DevBuf<int32_t> rec_index;
   DevBuf<char> rec_stage;    // fast / sq16 launches: one staging buffer the packed rows unpack into
   DevBuf<double> sum_agent, sum_scen;  // p2pmg_episode_summary: [A][16] and [S][16], allocated on first use
+  // the table digests (p2pmg_table_stats & co.): block partials and folded results of the last call, and
+  // the packed-policy snapshot [n_tables][n_states] u8 of p2pmg_policy_mark; all allocated on first use
+  DevBuf<double> td_part, td_out;
+  DevBuf<long long> td_cpart, td_cout;
+  DevBuf<uint8_t> policy_snap;
   DevBuf<float4> hp_lv;      // [A] per-agent heat-pump levels
   DevBuf<float4> thermal;    // [A] per-agent {setpoint, lower bound, upper bound, COP} (p2pmg_set_thermal)
   DevBuf<p2pmg::LearnRow> learn;  // [A] per-agent {alpha, gamma, comfort weight} (p2pmg_set_learning)
@@ -396,7 +401,8 @@ int p2pmg_create(const p2pmg_config* cfg, int device, p2pmg_ctx** out) {
   create_err.clear();
   if (cfg->n_scenarios <= 0 || cfg->n_agents <= 0 || cfg->rounds < 0 || cfg->horizon <= 0) return P2PMG_E_INVALID;
   if (cfg->rounds + 1 > p2pmg::kMaxRounds1) return P2PMG_E_UNSUPPORTED;
-  if (cfg->n_actions != 3) return P2PMG_E_UNSUPPORTED;
+  // 2 actions: a context that holds tables (set_q, get_q, the table digests) but runs no episode
+  if (cfg->n_actions != 3 && !(cfg->n_actions == 2 && cfg->learner == P2PMG_LEARNER_TABULAR)) return P2PMG_E_UNSUPPORTED;
   const int N = cfg->n_agents;
   // any community size a scenario's wave holds (get_community takes any n_agents, community.py:198-204)
   if (N > p2pmg::kMaxAgents) return P2PMG_E_UNSUPPORTED;
@@ -658,6 +664,99 @@ int p2pmg_get_q(p2pmg_ctx* c, int first, int count, void* host, int host_dtype) 
   return P2PMG_OK;
 }
 
+// ---- table digests: one pass of table_digest_kernel over tables [first, first + count) with the outputs
+// of the call switched on.  Each returns `count == 0` before this is reached.
+static int digest_range(p2pmg_ctx* c, int first, int count, const char* what) {
+  if (!c) return P2PMG_E_INVALID;
+  if (c->dqn) return fail(c, P2PMG_E_STATE, std::string(what) + ": DQN context has no Q-table");
+  if (first < 0 || count < 0 || (size_t)first + (size_t)count > c->n_tables)
+    return fail(c, P2PMG_E_INVALID, std::string(what) + ": bad table range");
+  return P2PMG_OK;
+}
+
+static p2pmg::TableDigestParams digest_params(p2pmg_ctx* c, int first, int count) {
+  p2pmg::TableDigestParams p{};
+  p.q = static_cast<const char*>(c->q) + (size_t)first * c->n_states * kQPad * c->q_elem;
+  p.n_states = c->n_states;
+  p.n_actions = c->cfg.n_actions;
+  p.count = count;
+  p.bpt = p2pmg::table_digest_blocks(count, c->n_states);
+  p.dword = c->n_states % 4 == 0 ? 1 : 0;  // every table's bytes then start 4-byte aligned
+  return p;
+}
+
+int p2pmg_table_stats(p2pmg_ctx* c, int first, int count, double* stats) {
+  RC_TRY(digest_range(c, first, count, "table_stats"));
+  if (count == 0) return P2PMG_OK;
+  if (!stats) return fail(c, P2PMG_E_INVALID, "table_stats: null output");
+  p2pmg::TableDigestParams p = digest_params(c, first, count);
+  HIP_TRY(c, c->td_part.grow((size_t)count * p.bpt * P2PMG_TABLE_STATS));
+  HIP_TRY(c, c->td_out.grow((size_t)count * P2PMG_TABLE_STATS));
+  p.stat_part = c->td_part;
+  p.stat_out = c->td_out;
+  HIP_TRY(c, p2pmg::launch_table_digest(p, c->cfg.q_dtype, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(stats, c->td_out, (size_t)count * P2PMG_TABLE_STATS * sizeof(double), hipMemcpyDeviceToHost,
+                            c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return P2PMG_OK;
+}
+
+int p2pmg_greedy_policy(p2pmg_ctx* c, int first, int count, uint8_t* policy) {
+  RC_TRY(digest_range(c, first, count, "greedy_policy"));
+  if (count == 0) return P2PMG_OK;
+  if (!policy) return fail(c, P2PMG_E_INVALID, "greedy_policy: null output");
+  const size_t bytes = (size_t)count * c->n_states;
+  DevBuf<uint8_t> staging;
+  HIP_TRY(c, staging.alloc(bytes));
+  p2pmg::TableDigestParams p = digest_params(c, first, count);
+  p.policy = staging;
+  HIP_TRY(c, p2pmg::launch_table_digest(p, c->cfg.q_dtype, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(policy, staging, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return P2PMG_OK;
+}
+
+int p2pmg_policy_mark(p2pmg_ctx* c) {
+  RC_TRY(digest_range(c, 0, 0, "policy_mark"));
+  const bool fresh = !c->policy_snap;
+  if (fresh && c->policy_snap.alloc(c->n_tables * c->n_states) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, P2PMG_E_NOMEM, "policy_mark: the policy snapshot ([n_tables][n_states] bytes)");
+  }
+  p2pmg::TableDigestParams p = digest_params(c, 0, (int)c->n_tables);
+  p.policy = c->policy_snap;
+  hipError_t e = p2pmg::launch_table_digest(p, c->cfg.q_dtype, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    if (fresh) c->policy_snap.release();  // no half-written first snapshot
+    return fail(c, P2PMG_E_HIP, std::string("policy_mark: ") + hipGetErrorString(e));
+  }
+  return P2PMG_OK;
+}
+
+int p2pmg_policy_changes(p2pmg_ctx* c, int first, int count, int64_t* changed, int64_t* newly_visited, int remark) {
+  RC_TRY(digest_range(c, first, count, "policy_changes"));
+  if (!c->policy_snap) return fail(c, P2PMG_E_STATE, "policy_changes: p2pmg_policy_mark first");
+  if (count == 0) return P2PMG_OK;
+  if (!changed) return fail(c, P2PMG_E_INVALID, "policy_changes: null output");
+  p2pmg::TableDigestParams p = digest_params(c, first, count);
+  HIP_TRY(c, c->td_cpart.grow((size_t)count * p.bpt * 2));
+  HIP_TRY(c, c->td_cout.grow((size_t)count * 2));
+  p.snap = c->policy_snap.get() + (size_t)first * c->n_states;
+  p.remark = remark ? 1 : 0;
+  p.chg_part = c->td_cpart;
+  p.chg_out = c->td_cout;
+  HIP_TRY(c, p2pmg::launch_table_digest(p, c->cfg.q_dtype, c->stream));
+  std::vector<long long> host((size_t)count * 2);
+  HIP_TRY(c, hipMemcpyAsync(host.data(), c->td_cout, host.size() * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < count; ++k) {
+    changed[k] = host[2 * (size_t)k];
+    if (newly_visited) newly_visited[k] = host[2 * (size_t)k + 1];
+  }
+  return P2PMG_OK;
+}
+
 // the unpacked record arrays as they exist now (ensure_records allocates them on demand)
 static void bind_records(p2pmg_ctx* c, EpisodeParams& p) {
   p.rec_reward = c->rec_f32[0];
@@ -895,6 +994,7 @@ static int update_chain_lag(p2pmg_ctx* c, const uint2* pre) {
 static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const ChainReq* ch) {
   if (!c || !args) return P2PMG_E_INVALID;
   if (c->dqn) return dqn_run_episode(c, args);
+  if (c->cfg.n_actions != 3) return fail(c, P2PMG_E_UNSUPPORTED, "run_episode: the kernels act on 3 actions (this context only holds tables)");
   if (!c->have_env || !c->have_prof || !c->have_params)
     return fail(c, P2PMG_E_STATE, "run_episode: env, profiles and agent params must be set first");
   const bool train = args->mode == P2PMG_MODE_TRAIN;
@@ -984,6 +1084,7 @@ int p2pmg_run_episodes_eps(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, 
 // n episodes at epsilons[k]; with c->eps_table, at the rows of c->eps_tab instead (epsilons: scenario 0's)
 static int run_episodes_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, int n, const double* epsilons, int next_n,
                              const double* next_epsilons) {
+  if (c->cfg.n_actions != 3) return fail(c, P2PMG_E_UNSUPPORTED, "run_episodes: the kernels act on 3 actions (this context only holds tables)");
   if (!c->dqn && (!c->have_env || !c->have_prof || !c->have_params))
     return fail(c, P2PMG_E_STATE, "run_episodes: env, profiles and agent params must be set first");
   // at least one full chain's worth, so a caller's chains never reallocate
@@ -1650,6 +1751,7 @@ int p2pmg_q_calls(p2pmg_ctx* c, int n, const int32_t* agents, const float* s_obs
   if (!c || n < 0 || !agents || !s_obs || !codes || !actions_out || !q_out) return P2PMG_E_INVALID;
   if (train && (!rewards || !ns_obs)) return fail(c, P2PMG_E_INVALID, "q_calls: train needs rewards and ns_obs");
   if (c->dqn) return fail(c, P2PMG_E_STATE, "q_calls: DQN context has no Q-table");
+  if (c->cfg.n_actions != 3) return fail(c, P2PMG_E_UNSUPPORTED, "q_calls: the kernels act on 3 actions (this context only holds tables)");
   for (int k = 0; k < n; ++k)
     if (agents[k] < 0 || (size_t)agents[k] >= c->n_tables) return fail(c, P2PMG_E_INVALID, "q_calls: agent out of range");
   if (n == 0) return P2PMG_OK;

@@ -171,6 +171,44 @@ class DeviceCommunityBatch:
         code = _lib.Q_F64 if dtype == np.float64 else _lib.Q_F32
         self._chk(self.L.p2pmg_set_q(self._ctx, first, t.shape[0], t.ctypes.data, code), "set_q")
 
+    # ----------------------------------------------------------------- table digests (on the device)
+    def _table_range(self, first, count):
+        return int(first), int(self.n_tables - first if count is None else count)
+
+    def table_stats(self, first: int = 0, count: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """Coverage, value range and greedy-action histogram of tables [first, first + count), reduced
+        on the device (p2pmg_table_stats): {"visited": [count] i64, "q_min", "q_max", "abs_max":
+        [count] f64, "greedy": [count, n_actions] i64 (visited rows per greedy action)}."""
+        first, count = self._table_range(first, count)
+        out = np.zeros((max(count, 0), _lib.TABLE_STATS), np.float64)
+        self._chk(self.L.p2pmg_table_stats(self._ctx, first, count, out.ctypes.data), "table_stats")
+        na = self.q_shape[-1]
+        return {"visited": out[:, 0].astype(np.int64), "q_min": out[:, 1].copy(), "q_max": out[:, 2].copy(),
+                "abs_max": out[:, 3].copy(), "greedy": out[:, 4:4 + na].astype(np.int64)}
+
+    def greedy_policy(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """u8 [count, n_time, n_temp, n_bal, n_p2p]: each state's greedy action (first maximum, rl.py:116),
+        or 255 (_lib.POLICY_UNVISITED) where the row is all zero (p2pmg_greedy_policy)."""
+        first, count = self._table_range(first, count)
+        out = np.zeros((max(count, 0), *self.q_shape[:-1]), np.uint8)
+        self._chk(self.L.p2pmg_greedy_policy(self._ctx, first, count, out.ctypes.data), "greedy_policy")
+        return out
+
+    def policy_mark(self):
+        """Snapshot every table's packed greedy policy on the device (p2pmg_policy_mark)."""
+        self._chk(self.L.p2pmg_policy_mark(self._ctx), "policy_mark")
+
+    def policy_changes(self, first: int = 0, count: Optional[int] = None, remark: bool = True) -> Dict[str, np.ndarray]:
+        """{"changed": [count] i64 states whose greedy action differs from the snapshot's, "newly_visited":
+        [count] i64 states unvisited in the snapshot and visited now}; remark: the same pass makes the
+        current policy of these tables the snapshot (p2pmg_policy_changes)."""
+        first, count = self._table_range(first, count)
+        ch = np.zeros(max(count, 0), np.int64)
+        nv = np.zeros(max(count, 0), np.int64)
+        self._chk(self.L.p2pmg_policy_changes(self._ctx, first, count, ch.ctypes.data, nv.ctypes.data,
+                                              int(bool(remark))), "policy_changes")
+        return {"changed": ch, "newly_visited": nv}
+
     # ----------------------------------------------------------------- heterogeneous agents / storage
     def set_hp_levels(self, levels):
         """Per-agent heat-pump power of actions 0..2 in W, [S, N, 3] (0 for agents without one)."""

@@ -27,6 +27,26 @@ def _as_obs(state) -> np.ndarray:
     return np.asarray(x, dtype=np.float32).reshape(-1, 4)
 
 
+def table_digest(q_table: np.ndarray) -> Tuple[np.ndarray, dict]:
+    """include/p2pmg.h's table digests of one table [..., n_actions] on the host, for an actor whose table
+    is not on a device: (packed greedy policy u8 [...], 255 = unvisited row; the p2pmg_table_stats
+    fields).  A row is visited iff any entry != 0; its greedy action is the first maximum (rl.py:116)."""
+    q = np.asarray(q_table)
+    na = q.shape[-1]
+    visited = (q != 0).any(axis=-1)
+    greedy = np.zeros(q.shape[:-1], np.uint8)
+    best = q[..., 0]
+    for k in range(1, na):  # the device's scan: strictly greater replaces
+        better = q[..., k] > best
+        best = np.where(better, q[..., k], best)
+        greedy[better] = k
+    lo, hi = np.float64(q.min()), np.float64(q.max())
+    stats = {"visited": np.int64(visited.sum()), "q_min": lo + 0.0, "q_max": hi + 0.0,
+             "abs_max": np.float64(max(-lo, hi)) + 0.0,
+             "greedy": np.array([(visited & (greedy == k)).sum() for k in range(na)], np.int64)}
+    return np.where(visited, greedy, np.uint8(255)).astype(np.uint8), stats
+
+
 class ActorInterface(ABC):
     @abstractmethod
     def __call__(self, state, *args, **kwargs): ...
@@ -110,6 +130,20 @@ class QActor(ActorInterface):
             self._host_table = np.array(q_table, dtype=np.float64)
         else:
             self._engine.set_q(q_table[None], first=self._slot)
+
+    def greedy_policy(self) -> np.ndarray:
+        """u8 (n_time, n_temp, n_balance, n_p2p): every state's greedy action, 255 where the row was
+        never written.  Bound: packed on the device (p2pmg_greedy_policy), 1/32 of the f64 table."""
+        if self._engine is None:
+            return table_digest(self.q_table)[0]
+        return self._engine.greedy_policy(first=self._slot, count=1)[0]
+
+    def table_stats(self) -> dict:
+        """{"visited", "q_min", "q_max", "abs_max": scalars, "greedy": [n_actions] i64} of this actor's
+        table (p2pmg_table_stats on the device when bound)."""
+        if self._engine is None:
+            return table_digest(self.q_table)[1]
+        return {k: v[0] for k, v in self._engine.table_stats(first=self._slot, count=1).items()}
 
     def load_from_file(self, setting: str, implementation: str) -> None:
         self.set_qtable(np.load(os.path.join(MODELS_DIR, f"models_{implementation}", f"{setting}.npy")))
