@@ -504,6 +504,73 @@ int p2pmg_dqn_forward(p2pmg_ctx* ctx, int net, int n, const float* x, float* q);
 /* Trainer._train + update_targets (rl.py:307-359) of one network on a given batch [32][10] */
 int p2pmg_dqn_train_batch(p2pmg_ctx* ctx, int net, const float* batch, float* loss);
 
+/* The DQN policy map: what the table digests are for a Q-table, for a Q-network.  For each network the
+ * Q-MLP is evaluated ON THE DEVICE at every state of a rectangular grid of observations and at the three
+ * action values (ActorModel.greedy_action rl.py:188-196 over the state grid of data_analysis.py's
+ * plot_q_values_* and compare_decisions*), and only what was asked for reaches the host: one byte per
+ * state, eight numbers per network, the Q values themselves, or one count per network against a snapshot.
+ *
+ * Grid.  Four axes of f32 values, time[n0], temp[n1], balance[n2], p2p[n3].  State
+ * g = ((i0 n1 + i1) n2 + i2) n3 + i3 has the observation (time[i0], temp[i1], balance[i2], p2p[i3]): the
+ * reference's (time, temp, balance, p2p) order, time slowest, the order of p2pmg_get_q and
+ * p2pmg_greedy_policy.  G = n0 n1 n2 n3, every n >= 1, G <= 2^31 - 1 (else P2PMG_E_INVALID).
+ * p2pmg_dqn_set_grid uploads the axes; all four axes NULL (n is then ignored) restores the DEFAULT grid:
+ * the context's table shape (n_time_states .. n_p2p_states), each axis at its bins' centres, formed in f64
+ * and cast to f32: time (k + 1/2) / K, temp 2 (k - 1/2) / (K - 2) - 1, balance and p2p 2 (k + 1/2) / K - 1.
+ * The default needs n_temp_states >= 3 (else P2PMG_E_INVALID from every call until axes are set) and is in
+ * use until p2pmg_dqn_set_grid says otherwise.  On it, state g of a map is the state of row g of a table's
+ * packed policy (each centre falls in its own bin), so tabular and DQN policies compare byte for byte.
+ * p2pmg_dqn_get_grid returns the shape and, if axes != NULL, the n0 + n1 + n2 + n3 values in use,
+ * time | temp | balance | p2p.
+ *
+ * Q values.  q[g][a], a = 0, 1, 2 (action values 0, 1/2, 1), is what dqn_act_kernel and
+ * dqn_act_shared_kernel compute for that observation, bit for bit (oracle/dqn.py::act_q): layer 1 starts
+ * from p2p W1[3], then fmaf with balance, temp and time; the action term is z + b1, fmaf(0.5, W1[4], z) + b1
+ * or (z + W1[4]) + b1; layer 2 is the fmaf chain over k = 0..63 from +0 (the f32 MFMA's k order); layer 3
+ * is the pairwise tree over the 64 units, then + b3.  A byte of the map is therefore the action the act
+ * kernel takes at that observation when it does not explore.
+ *   greedy action  g = 0; for k = 1, 2 in order: if q[k] > q[g] then g = k.  The FIRST maximum.  There is no
+ *                  "unvisited" value: every byte is 0, 1 or 2.
+ * Networks are assumed NaN-free.  Every statistic is a count, a minimum or a maximum, so no launch shape
+ * or fold order changes a bit; f32 widens to f64 exactly; zeros are returned as +0.0.
+ *
+ * All calls: `which` is P2PMG_DQN_ONLINE or P2PMG_DQN_TARGET (else P2PMG_E_INVALID); networks are
+ * addressed as p2pmg_dqn_get_weights addresses them (A per-agent networks or 1 shared; first < 0,
+ * count < 0 or first + count > n_nets: P2PMG_E_INVALID); they are stream-ordered after earlier launches,
+ * synchronise before returning and read the weights as they are at the call.  Tabular context, or before
+ * p2pmg_dqn_setup: P2PMG_E_STATE.  count == 0: P2PMG_OK, nothing written.  A NULL output (both, for
+ * p2pmg_dqn_policy_map, which needs only one): P2PMG_E_INVALID.
+ *
+ * p2pmg_dqn_policy_map walks the networks (and, for grids beyond the bound, one network's states) in
+ * chunks: its device staging never exceeds P2PMG_DQN_MAP_STAGE_BYTES, whatever count x G is.
+ *
+ * p2pmg_dqn_map_stats: P2PMG_DQN_MAP_STATS f64 values per network, stats[k][.] for network first + k:
+ *    0 G           number of grid states
+ *    1 q_min       minimum over all G x 3 Q values
+ *    2 q_max       maximum over the same values
+ *    3 abs_max     maximum of |q| over the same values (= max(-q_min, q_max))
+ *    4..6 greedy[a]  number of states whose greedy action is a (fields 4..6 sum to field 0)
+ *    7 min_gap     minimum over the states of the f32 difference q[greedy] - max(the other two)
+ *
+ * Churn.  p2pmg_dqn_policy_mark stores the packed map of EVERY network of `which` in a snapshot
+ * [n_nets][G] u8 that the context owns on the device (one snapshot, whichever array it was taken of); the
+ * first call allocates it (P2PMG_E_NOMEM if that fails, and there is then no snapshot).
+ * p2pmg_dqn_policy_changes gives changed[k], the number of states of network first + k of `which` whose
+ * greedy action now differs from the snapshot's; remark != 0 overwrites the snapshot of networks
+ * [first, first + count), and of no other, in the same pass.  p2pmg_dqn_set_grid drops the snapshot.
+ * Before a mark, or after a grid change: P2PMG_E_STATE. */
+#define P2PMG_DQN_MAP_STATS 8
+#define P2PMG_DQN_MAP_STAGE_BYTES (32u << 20)
+int p2pmg_dqn_set_grid(p2pmg_ctx* ctx, const int32_t* n /* [4] */, const float* time, const float* temp,
+                       const float* balance, const float* p2p);
+int p2pmg_dqn_get_grid(p2pmg_ctx* ctx, int32_t* n /* [4] */, float* axes /* [n0 + n1 + n2 + n3] or NULL */);
+int p2pmg_dqn_policy_map(p2pmg_ctx* ctx, int which, int first, int count, uint8_t* policy /* [count][G] or NULL */,
+                         float* q /* [count][G][3] or NULL */);
+int p2pmg_dqn_map_stats(p2pmg_ctx* ctx, int which, int first, int count, double* stats /* [count][P2PMG_DQN_MAP_STATS] */);
+int p2pmg_dqn_policy_mark(p2pmg_ctx* ctx, int which);
+int p2pmg_dqn_policy_changes(p2pmg_ctx* ctx, int which, int first, int count, int64_t* changed /* [count] */,
+                             int remark);
+
 /* Shared network over several ranks (config 5): the gradient segments of every rank are gathered
  * once per env step, then every rank sums all of them in global segment order and takes the same
  * Adam step, so the replicas stay bit-identical.  With an RCCL communicator (p2pmg_comm_init) the

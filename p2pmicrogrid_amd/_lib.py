@@ -25,6 +25,7 @@ RNG_REPLAY, RNG_PHILOX = 0, 1
 REC = {"reward": 1, "cost": 2, "grid": 4, "p2p": 8, "t_in": 16, "action": 32, "index": 64, "loss": 128}
 GREEDY = 255
 TABLE_STATS = 8          # P2PMG_TABLE_STATS
+DQN_MAP_STATS = 8        # P2PMG_DQN_MAP_STATS
 POLICY_UNVISITED = 255   # P2PMG_POLICY_UNVISITED
 
 EXPORTS = [
@@ -48,6 +49,8 @@ EXPORTS = [
     "p2pmg_episode_summary",
     "p2pmg_set_learning", "p2pmg_get_learning", "p2pmg_run_episodes_eps",
     "p2pmg_table_stats", "p2pmg_greedy_policy", "p2pmg_policy_mark", "p2pmg_policy_changes",
+    "p2pmg_dqn_set_grid", "p2pmg_dqn_get_grid", "p2pmg_dqn_policy_map", "p2pmg_dqn_map_stats", "p2pmg_dqn_policy_mark",
+    "p2pmg_dqn_policy_changes",
 ]
 
 
@@ -172,6 +175,12 @@ def _declare(lib):
         "p2pmg_dqn_set_buffer": ([vp, i32, i32, vp, vp], i32),
         "p2pmg_dqn_forward": ([vp, i32, i32, vp, vp], i32),
         "p2pmg_dqn_train_batch": ([vp, i32, vp, vp], i32),
+        "p2pmg_dqn_set_grid": ([vp, vp, vp, vp, vp, vp], i32),      # n [4] i32, four f32 axes (all NULL: default)
+        "p2pmg_dqn_get_grid": ([vp, vp, vp], i32),                  # n [4] i32, axes f32 or NULL
+        "p2pmg_dqn_policy_map": ([vp, i32, i32, i32, vp, vp], i32),  # policy [count][G] u8, q [count][G][3] f32
+        "p2pmg_dqn_map_stats": ([vp, i32, i32, i32, vp], i32),      # [count][DQN_MAP_STATS] f64
+        "p2pmg_dqn_policy_mark": ([vp, i32], i32),
+        "p2pmg_dqn_policy_changes": ([vp, i32, i32, i32, vp, i32], i32),  # changed [count] i64
         "p2pmg_prepass_stats": ([vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], i32),
         "p2pmg_chain_lag": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int)], i32),
         "p2pmg_dqn_get_net_steps": ([vp, i32, i32, vp], i32),

@@ -277,6 +277,22 @@ class CommunityMicrogrid:
         per = [a.actor.table_stats() for a in self.agents]
         return {k: np.stack([np.asarray(p[k]) for p in per]) for k in per[0]}
 
+    def policy_maps(self, grid=None, q: bool = False):
+        """One policy map per DQNAgent (ActorModel.policy_map): u8 [N, n0, n1, n2, n3], the greedy action
+        of each agent's online network at every state of the grid; q=True: (maps, Q values f32
+        [N, n0, n1, n2, n3, 3]).  One device pass over the community's networks once they are on the
+        device and no grid is asked for."""
+        if not self._dqn:
+            raise RuntimeError("policy_maps(): only DQN communities have Q-networks (tabular: QActor.greedy_policy)")
+        nets = [a.actor.q_network for a in self.agents]
+        if grid is None and self._engine is not None and all(
+                n._engine is self._engine and n._which == "online" and n._slot == i for i, n in enumerate(nets)):
+            return self._engine.policy_map(0, len(self.agents), q=q)
+        per = [a.actor.policy_map(grid=grid, q=q) for a in self.agents]
+        if q:
+            return np.stack([p[0] for p in per]), np.stack([p[1] for p in per])
+        return np.stack(per)
+
     def run_days(self, days, summary: bool = False) -> List[Dict[str, np.ndarray]]:
         """run() of this community over several days in ONE greedy launch: a per-role-table engine
         (``shared_q="role"``) with one scenario per day, holding one copy of every agent's table

@@ -1,5 +1,5 @@
 // Internal declarations shared by the kernel units (device code + launchers: p2pmg_general.hip,
-// p2pmg_fast.hip, p2pmg_sq16.hip, p2pmg_small.hip, p2pmg_dqn.hip, p2pmg_summary.hip, p2pmg_tables.hip) and
+// p2pmg_fast.hip, p2pmg_sq16.hip, p2pmg_small.hip, p2pmg_dqn.hip, p2pmg_dqn_map.hip, p2pmg_summary.hip, p2pmg_tables.hip) and
 // p2pmg_runtime.cpp (context, C ABI).  Not part of the public ABI (include/p2pmg.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -166,6 +166,36 @@ constexpr int kActAdamSegs = 8;
 // network's MFMA act kernel, at most kActAdamSegs segments)
 bool dqn_act_fuses_adam(const DqnParams& p);
 hipError_t launch_dqn_forward(const float* theta, int n, const float* x, float* q, hipStream_t stream);
+
+// the DQN policy map (p2pmg_dqn_map.hip): p2pmg_dqn_policy_map, p2pmg_dqn_map_stats, p2pmg_dqn_policy_mark
+// and p2pmg_dqn_policy_changes are one pass over `count` networks and the states [g_begin, g_begin +
+// g_count) of the grid, with different outputs switched on
+constexpr int kDqnMapStats = 8;
+struct DqnMapPart {      // one block's results over its states of one network
+  float lo, hi, gap;     // min / max over the Q values, min over states of q[greedy] - max(the other two)
+  uint32_t n_g[3];       // states per greedy action
+  uint32_t n_chg;        // compare: states whose greedy action differs from the snapshot's
+  uint32_t pad;
+};
+struct DqnMapParams {
+  const float* theta;    // [count][kNetStride]: the first network of the launch
+  int count;
+  unsigned bpn;          // blocks per network (dqn_map_blocks): a block never spans networks
+  uint32_t n[4];         // grid shape (time, temp, balance, p2p), time slowest
+  const float* axes;     // [n0 + n1 + n2 + n3] axis values, time | temp | balance | p2p
+  uint32_t g_begin, g_count;  // the states of the launch; the outputs below are indexed from g_begin
+  int dword;             // 1: policy / snapshot bytes move as dwords (g_count % 4 == 0, 4-byte aligned bases)
+  int remark;            // compare: overwrite the snapshot with the current map in the same pass
+  uint8_t* policy;       // [count][g_count] or null
+  float* q;              // [count][g_count][3] or null
+  uint8_t* snap;         // compare: [count][g_count] snapshot of the same networks, or null
+  DqnMapPart* part;      // [count][bpn] block partials (stats, compare) or null
+  double* stat_out;      // [count][kDqnMapStats] or null
+  long long* chg_out;    // [count] or null
+};
+unsigned dqn_map_blocks(int count, uint32_t g_count);
+// count <= 0 or g_count == 0 launches nothing
+hipError_t launch_dqn_map(const DqnMapParams& p, hipStream_t stream);
 
 struct RcParams {
   float inv_ci, inv_cm, inv_ri, inv_re, inv_rvent, c_in, c_m, solar, cop, spm, slot;

@@ -28,6 +28,7 @@ from .engine import DeviceCommunityBatch
 F32 = np.float32
 N_PARAMS = _lib.DQN_PARAMS
 WHICH = {"online": _lib.DQN_ONLINE, "target": _lib.DQN_TARGET, "adam_m": _lib.DQN_ADAM_M, "adam_v": _lib.DQN_ADAM_V}
+MAP_WHICH = {"online": _lib.DQN_ONLINE, "target": _lib.DQN_TARGET}  # arrays the policy map reads
 MODES = {"train": _lib.MODE_TRAIN, "greedy": _lib.MODE_GREEDY, "fill": _lib.MODE_FILL}
 ACTION_VALUES = np.array([0.0, 0.5, 1.0], dtype=F32)  # ActorModel.actions rl.py:153
 
@@ -186,6 +187,84 @@ class DeviceDQNBatch(DeviceCommunityBatch):
         obs = np.asarray(obs, F32).reshape(-1, 4)
         x = np.concatenate([np.repeat(obs, 3, axis=0), np.tile(ACTION_VALUES, len(obs))[:, None]], axis=1)
         return self.forward(x, net).reshape(-1, 3)
+
+    # ----------------------------------------------------------------- the policy map
+    def _map_range(self, first: int, count: Optional[int], which: str):
+        """(which code, first, count) of a map call, checked before any device call."""
+        if which not in MAP_WHICH:
+            raise ValueError(f"which must be 'online' or 'target', not {which!r}")
+        first = int(first)
+        count = self.n_nets - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > self.n_nets:
+            raise ValueError(f"networks [{first}, {first + count}) outside [0, {self.n_nets})")
+        return MAP_WHICH[which], first, count
+
+    def set_policy_grid(self, time=None, temp=None, balance=None, p2p=None):
+        """The grid of observations of the map calls: four f32 axes, state order (time, temp, balance,
+        p2p), time slowest.  No axis: back to the default, the table shape at its bins' centres.  A new
+        grid drops the map_mark() snapshot."""
+        axes = (time, temp, balance, p2p)
+        if all(a is None for a in axes):
+            self._chk(self.L.p2pmg_dqn_set_grid(self._ctx, None, None, None, None, None), "dqn_set_grid")
+            return
+        if any(a is None for a in axes):
+            raise ValueError("set_policy_grid: give all four axes, or none for the default grid")
+        ax = [np.ascontiguousarray(np.asarray(a, F32).reshape(-1)) for a in axes]
+        if any(a.size == 0 for a in ax):
+            raise ValueError("set_policy_grid: every axis needs at least one value")
+        if int(np.prod([a.size for a in ax], dtype=object)) > 2 ** 31 - 1:
+            raise ValueError("set_policy_grid: more than 2^31 - 1 grid states")
+        n = np.array([a.size for a in ax], np.int32)
+        self._chk(self.L.p2pmg_dqn_set_grid(self._ctx, n.ctypes.data, *[a.ctypes.data for a in ax]), "dqn_set_grid")
+
+    def policy_grid(self):
+        """The axes in use: (time, temp, balance, p2p) f32 arrays."""
+        n = np.zeros(4, np.int32)
+        self._chk(self.L.p2pmg_dqn_get_grid(self._ctx, n.ctypes.data, None), "dqn_get_grid")
+        ax = np.empty(int(n.sum()), F32)
+        self._chk(self.L.p2pmg_dqn_get_grid(self._ctx, n.ctypes.data, ax.ctypes.data), "dqn_get_grid")
+        return tuple(np.split(ax, np.cumsum(n)[:-1]))
+
+    def _grid_shape(self):
+        n = np.zeros(4, np.int32)
+        self._chk(self.L.p2pmg_dqn_get_grid(self._ctx, n.ctypes.data, None), "dqn_get_grid")
+        return tuple(int(k) for k in n)
+
+    def policy_map(self, first: int = 0, count: Optional[int] = None, which: str = "online", q: bool = False):
+        """The greedy action (0, 1, 2: first maximum) of networks [first, first + count) at every state of
+        the grid, evaluated on the device: u8 [count, n0, n1, n2, n3]; q=True: (policy, Q values f32
+        [count, n0, n1, n2, n3, 3]), the act kernels' bits."""
+        w, first, count = self._map_range(first, count, which)
+        shape = self._grid_shape()
+        pol = np.empty((count, *shape), np.uint8)
+        qv = np.empty((count, *shape, 3), F32) if q else None
+        self._chk(self.L.p2pmg_dqn_policy_map(self._ctx, w, first, count, pol.ctypes.data,
+                                              qv.ctypes.data if q else None), "dqn_policy_map")
+        return (pol, qv) if q else pol
+
+    def map_stats(self, first: int = 0, count: Optional[int] = None, which: str = "online") -> dict:
+        """Per network over the grid: {"states": i64 [count], "q_min", "q_max", "abs_max", "min_gap": f64
+        [count], "greedy": i64 [count, 3]} (p2pmg_dqn_map_stats)."""
+        w, first, count = self._map_range(first, count, which)
+        st = np.zeros((count, _lib.DQN_MAP_STATS), np.float64)
+        self._chk(self.L.p2pmg_dqn_map_stats(self._ctx, w, first, count, st.ctypes.data), "dqn_map_stats")
+        return {"states": st[:, 0].astype(np.int64), "q_min": st[:, 1].copy(), "q_max": st[:, 2].copy(),
+                "abs_max": st[:, 3].copy(), "greedy": st[:, 4:7].astype(np.int64), "min_gap": st[:, 7].copy()}
+
+    def map_mark(self, which: str = "online"):
+        """Snapshot the packed map of every network of ``which`` on the device (p2pmg_dqn_policy_mark)."""
+        w, _, _ = self._map_range(0, 0, which)
+        self._chk(self.L.p2pmg_dqn_policy_mark(self._ctx, w), "dqn_policy_mark")
+
+    def map_changes(self, first: int = 0, count: Optional[int] = None, which: str = "online",
+                    remark: bool = True) -> np.ndarray:
+        """i64 [count]: states whose greedy action differs from the snapshot's; remark=True rewrites the
+        snapshot of exactly these networks in the same pass."""
+        w, first, count = self._map_range(first, count, which)
+        out = np.zeros(count, np.int64)
+        self._chk(self.L.p2pmg_dqn_policy_changes(self._ctx, w, first, count, out.ctypes.data, 1 if remark else 0),
+                  "dqn_policy_changes")
+        return out
 
     def train_batch(self, s, a, r, ns, net: int = 0) -> float:
         """Trainer._train + update_targets (rl.py:307-359) on one batch of 32 transitions."""

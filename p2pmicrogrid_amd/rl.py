@@ -329,6 +329,42 @@ class ActorModel(ActorInterface):
         q = self._q_network(np.repeat(s, 3, axis=0), self.actions[:, None])   # (3, 1)
         return np.expand_dims(self.actions[int(np.argmax(q[:, 0]))], axis=0), q
 
+    def _map_engine(self, grid):
+        """(engine, slot, temporary) for a map of this actor's network: its own engine on that engine's
+        grid, else a one-network engine with ``grid`` (or the default)."""
+        net = self._q_network
+        if grid is None and net._engine is not None and net._which == "online":
+            return net._engine, net._slot, False
+        from .dqn import DeviceDQNBatch
+        eng = DeviceDQNBatch(1, 1, 0, 1, device=setup.device, init_seed=None)  # a bound engine keeps its grid
+        eng.set_weights("online", net.flat_weights()[None])
+        if grid is not None:
+            eng.set_policy_grid(*grid)
+        return eng, 0, True
+
+    def policy_map(self, grid=None, q: bool = False):
+        """u8 (n0, n1, n2, n3): greedy_action (first maximum over the action values 0, .5, 1) at every state
+        of ``grid`` = (time, temp, balance, p2p) axes; None: the bound engine's grid, else the default
+        (the 20^4 table shape at its bins' centres, where byte g is row g of QActor.greedy_policy()).
+        q=True: (policy, Q values f32 (n0, n1, n2, n3, 3)).  One device pass (p2pmg_dqn_policy_map)."""
+        eng, slot, tmp = self._map_engine(grid)
+        try:
+            out = eng.policy_map(first=slot, count=1, q=q)
+            return (out[0][0], out[1][0]) if q else out[0]
+        finally:
+            if tmp:
+                eng.close()
+
+    def map_stats(self, grid=None) -> dict:
+        """{"states", "q_min", "q_max", "abs_max", "min_gap": scalars, "greedy": [3] i64} of this actor's
+        network over the grid (p2pmg_dqn_map_stats)."""
+        eng, slot, tmp = self._map_engine(grid)
+        try:
+            return {k: v[0] for k, v in eng.map_stats(first=slot, count=1).items()}
+        finally:
+            if tmp:
+                eng.close()
+
     def decay_exploration(self) -> None:
         self._epsilon *= self._decay  # no floor for the DQN actor (rl.py:196-197)
 
