@@ -16,6 +16,7 @@
  *   p2pmg_set_agent_params     get_community max_in                      community.py:216-227
  *   p2pmg_set_temperatures     HPHeating.__init__/reset T0               heating.py:101-104,145-152
  *   p2pmg_get_q / p2pmg_set_q  QActor.q_table / set_qtable               rl.py:76-81 (layout (20,20,20,20,3))
+ *   p2pmg_get_q_sparse / p2pmg_set_q_sparse   QActor.save_to_file / load_from_file, for a batch   rl.py:83-87
  *   p2pmg_rc_step              heating.temperature_simulation (batched)  heating.py:37-56
  *   p2pmg_state_indices        QActor._get_state_indices (batched)       rl.py:89-95
  *   p2pmg_replay_decode        np.random rand()/choice(3) consumption    rl.py:100-111 (legacy MT19937)
@@ -37,7 +38,7 @@
 extern "C" {
 #endif
 
-#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag, p2pmg_set_learning, p2pmg_get_learning, p2pmg_run_episodes_eps, p2pmg_table_stats, p2pmg_greedy_policy, p2pmg_policy_mark, p2pmg_policy_changes, n_actions = 2 table-only contexts) */
+#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag, p2pmg_set_learning, p2pmg_get_learning, p2pmg_run_episodes_eps, p2pmg_table_stats, p2pmg_greedy_policy, p2pmg_policy_mark, p2pmg_policy_changes, n_actions = 2 table-only contexts, p2pmg_sparse_count, p2pmg_get_q_sparse, p2pmg_set_q_sparse, p2pmg_copy_q) */
 
 typedef struct p2pmg_ctx p2pmg_ctx;
 
@@ -262,6 +263,68 @@ int p2pmg_greedy_policy(p2pmg_ctx* ctx, int first, int count, uint8_t* policy /*
 int p2pmg_policy_mark(p2pmg_ctx* ctx);
 int p2pmg_policy_changes(p2pmg_ctx* ctx, int first, int count, int64_t* changed /* [count] */,
                          int64_t* newly_visited /* [count] or NULL */, int remark);
+
+/* Sparse table checkpoints: the tables taken home and brought back without their zeros.  p2pmg_get_q and
+ * p2pmg_set_q move count x n_states x n_actions elements whatever the tables hold; a table that training
+ * has touched in a few hundred or thousand of its 160 000 rows travels here as those rows only, compacted
+ * ON THE DEVICE by a streaming pass like the digests', and comes back by a scatter.
+ *
+ * All four calls address tables as p2pmg_get_q does (A per-agent tables, 1 shared table or N role
+ * tables), are stream-ordered after earlier launches and synchronise before returning.  They do not apply
+ * the pending int64 delta of a shared or role context and do not touch the policy snapshot.  DQN context:
+ * P2PMG_E_STATE.  first < 0, count < 0, first + count > n_tables or a NULL required pointer:
+ * P2PMG_E_INVALID.  count == 0: P2PMG_OK, nothing read or written.  n_states > 2^31 - 1 (row indices are
+ * int32): P2PMG_E_UNSUPPORTED.
+ *
+ * Definitions, bit for bit.
+ *   stored row   a row is stored iff at least one of its n_actions entries has a NON-ZERO BIT PATTERN.  An
+ *                entry of -0.0 therefore counts.  The padding columns never count and are never exported.
+ *                This is a superset of the digests' "visited" (any entry != 0.0): the two differ exactly
+ *                in the rows whose entries are all zeros with at least one -0.0, which are stored and not
+ *                visited.  NaN entries are non-zero bits like any other.
+ *   sparse form  of tables [first, first + count), three arrays:
+ *                  n_rows[count]            int64, the stored rows of each table
+ *                  rows[total]              int32, the state indices (row numbers in p2pmg_get_q's order) of
+ *                                           the stored rows, table after table, STRICTLY ASCENDING inside
+ *                                           each table; total = sum of n_rows
+ *                  values[total][n_actions] host dtype, the entries of those rows in the same order
+ *                Conversion between the table's dtype and the host dtype is p2pmg_get_q's / p2pmg_set_q's
+ *                (a C cast per entry; same dtype: the bits).  Storedness is always decided on the TABLE's
+ *                own bits, before any conversion.  The order is part of the definition: the same tables
+ *                give the same bytes whatever the launch shape (positions come from an ordered scan of
+ *                counts, never from atomics).
+ *   round trip   zero the tables, then import the sparse form taken in the table's own dtype: the
+ *                n_actions entries of every row are reproduced bit for bit (an all-+0.0 row is simply
+ *                absent).
+ *
+ * Staging.  Neither direction allocates by n_states: the device staging of a call holds one RUN of whole
+ * tables whose stored rows fit P2PMG_SPARSE_STAGE_BYTES, at 4 + n_actions * sizeof(host dtype) bytes a
+ * row; a run always holds at least one table, so a single table with more stored rows than that is a run
+ * of its own and the staging grows to it.  The context keeps the staging for the next call.
+ *
+ * p2pmg_sparse_count: one counting pass; n_rows[k] = stored rows of table first + k.
+ * p2pmg_get_q_sparse: counts, then exports.  It ALWAYS writes n_rows.  If the total exceeds `capacity` (the
+ *   rows that `rows` and `values` have room for) it returns P2PMG_E_INVALID with `rows` and `values`
+ *   untouched: size the buffers from n_rows (or from p2pmg_sparse_count) and call again.  rows and values
+ *   are required only when the total is not 0.
+ * p2pmg_set_q_sparse: the host checks the whole form BEFORE anything is uploaded or zeroed: every
+ *   n_rows[k] in [0, n_states], every index in [0, n_states), indices strictly ascending inside each table
+ *   (so no duplicates, and the scatter has no write race).  A violation returns P2PMG_E_INVALID and the
+ *   tables are unchanged.  zero_first != 0 zeroes tables [first, first + count) first, padding included
+ *   (not the pending delta: that is p2pmg_zero_q's); zero_first == 0 overlays: only the listed rows are
+ *   overwritten.  The padding of a written row is 0.  rows and values are required only when the total
+ *   is not 0.
+ * p2pmg_copy_q: tables [dst_first, dst_first + dst_count) become bit copies of table src, padding
+ *   included, device to device (warm-starting many communities from one).  src outside 0 .. n_tables-1 or
+ *   inside the destination range: P2PMG_E_INVALID. */
+#define P2PMG_SPARSE_STAGE_BYTES (8u << 20)
+int p2pmg_sparse_count(p2pmg_ctx* ctx, int first, int count, int64_t* n_rows /* [count] */);
+int p2pmg_get_q_sparse(p2pmg_ctx* ctx, int first, int count, int64_t capacity, int64_t* n_rows /* [count] */,
+                       int32_t* rows /* [capacity] */, void* values /* [capacity][n_actions] */, int host_dtype);
+int p2pmg_set_q_sparse(p2pmg_ctx* ctx, int first, int count, const int64_t* n_rows /* [count] */,
+                       const int32_t* rows /* [total] */, const void* values /* [total][n_actions] */, int host_dtype,
+                       int zero_first);
+int p2pmg_copy_q(p2pmg_ctx* ctx, int src, int dst_first, int dst_count);
 
 /* the hot path */
 int p2pmg_run_episode(p2pmg_ctx* ctx, const p2pmg_episode_args* args);

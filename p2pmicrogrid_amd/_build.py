@@ -17,7 +17,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libp2pmg.so")
-HEADERS = ["p2pmg_internal.h", "p2pmg_device.h", "p2pmg_tabular.h", "p2pmg_fastmath.h", "p2pmg_plan.h",
+HEADERS = ["p2pmg_internal.h", "p2pmg_device.h", "p2pmg_tabular.h", "p2pmg_fastmath.h", "p2pmg_plan.h", "p2pmg_sparse.h",
            "p2pmg_dqn_ops.h", os.path.join(ROOT, "include", "p2pmg.h")]
 ARCH = os.environ.get("P2PMG_ARCH", "gfx950")
 
@@ -41,6 +41,7 @@ UNITS = [
     ("p2pmg_tables.hip", None, [], "p2pmg_tables.o"),
     ("p2pmg_runtime.cpp", None, [], "p2pmg_runtime.o"),
     ("p2pmg_plan.cpp", None, [], "p2pmg_plan.o"),
+    ("p2pmg_sparse.cpp", None, [], "p2pmg_sparse.o"),
 ]
 
 

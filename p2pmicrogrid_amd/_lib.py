@@ -27,6 +27,7 @@ GREEDY = 255
 TABLE_STATS = 8          # P2PMG_TABLE_STATS
 DQN_MAP_STATS = 8        # P2PMG_DQN_MAP_STATS
 POLICY_UNVISITED = 255   # P2PMG_POLICY_UNVISITED
+SPARSE_STAGE_BYTES = 8 << 20  # P2PMG_SPARSE_STAGE_BYTES
 
 EXPORTS = [
     "p2pmg_abi_version", "p2pmg_config_default", "p2pmg_create", "p2pmg_destroy", "p2pmg_last_error", "p2pmg_last_kernel",
@@ -51,6 +52,7 @@ EXPORTS = [
     "p2pmg_table_stats", "p2pmg_greedy_policy", "p2pmg_policy_mark", "p2pmg_policy_changes",
     "p2pmg_dqn_set_grid", "p2pmg_dqn_get_grid", "p2pmg_dqn_policy_map", "p2pmg_dqn_map_stats", "p2pmg_dqn_policy_mark",
     "p2pmg_dqn_policy_changes",
+    "p2pmg_sparse_count", "p2pmg_get_q_sparse", "p2pmg_set_q_sparse", "p2pmg_copy_q",
 ]
 
 
@@ -127,6 +129,11 @@ def _declare(lib):
         "p2pmg_greedy_policy": ([vp, i32, i32, vp], i32),          # [count][n_states] u8
         "p2pmg_policy_mark": ([vp], i32),
         "p2pmg_policy_changes": ([vp, i32, i32, vp, vp, i32], i32),  # changed, newly_visited [count] i64
+        "p2pmg_sparse_count": ([vp, i32, i32, vp], i32),            # n_rows [count] i64
+        # capacity, n_rows [count] i64, rows [capacity] i32, values [capacity][n_actions], host dtype
+        "p2pmg_get_q_sparse": ([vp, i32, i32, C.c_int64, vp, vp, vp, i32], i32),
+        "p2pmg_set_q_sparse": ([vp, i32, i32, vp, vp, vp, i32, i32], i32),  # n_rows, rows, values, host dtype, zero_first
+        "p2pmg_copy_q": ([vp, i32, i32, i32], i32),                 # src, dst_first, dst_count
         "p2pmg_run_episode": ([vp, C.POINTER(EpisodeArgs)], i32),
         "p2pmg_run_episodes": ([vp, C.POINTER(EpisodeArgs), i32, dp, i32, vp], i32),
         "p2pmg_run_episodes_eps": ([vp, C.POINTER(EpisodeArgs), i32, dp], i32),  # eps [n][S] f64

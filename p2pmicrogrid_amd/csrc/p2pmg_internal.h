@@ -314,6 +314,42 @@ struct TableDigestParams {
 unsigned table_digest_blocks(int count, size_t n_states);
 // stats and compare exclude each other; the fold launch follows the pass on the stream
 hipError_t launch_table_digest(const TableDigestParams& p, int q_dtype, hipStream_t stream);
+// the sparse table checkpoints (p2pmg_tables.hip): p2pmg_sparse_count, p2pmg_get_q_sparse and
+// p2pmg_set_q_sparse.  A row is STORED iff one of its n_actions entries has a non-zero bit pattern.
+// Export is a count pass (stored rows per block), an offset pass (one wave per table: the block counts
+// become exclusive offsets inside their table, and the table's total) and a scatter pass with the count
+// pass's block-to-rows mapping; the order of the output comes from the scan, never from atomics.
+struct SparseParams {
+  const void* q;         // the first table of the launch: [count][n_states][kQPad] f64 | f32
+  size_t n_states;
+  int n_actions, count;
+  unsigned bpt;          // blocks per table (sparse_blocks): a block never spans tables
+  unsigned rpb;          // rows per block, a multiple of the pass's tile: block b owns rows [b * rpb, (b + 1) * rpb) of its table
+  uint32_t* blk;         // [count][bpt]: the count pass's stored rows per block, then (offset pass) their exclusive scan per table
+  long long* total;      // offset pass: [count] stored rows per table
+  const long long* base; // scatter: [count] where each table's rows begin in out_rows / out_vals
+  int32_t* out_rows;     // scatter: state indices of the stored rows, table after table, ascending
+  void* out_vals;        // scatter: their [n_actions] entries in the host dtype
+};
+// bpt and rpb for `count` tables of n_states rows; one call of the C ABI uses one mapping for all its passes
+void sparse_blocks(int count, size_t n_states, unsigned* bpt, unsigned* rpb);
+// count pass then offset pass on the stream; count <= 0 or n_states == 0 launches nothing
+hipError_t launch_sparse_count(const SparseParams& p, int q_dtype, hipStream_t stream);
+// p.blk as launch_sparse_count left it for these tables (the tables unchanged since)
+hipError_t launch_sparse_scatter(const SparseParams& p, int q_dtype, int host_dtype, hipStream_t stream);
+// import: one thread per listed row i < total writes one padded row (padding 0) of table t, where
+// base[t] <= i < base[t + 1] (base[count] stands for total and is not read); rows within [0, n_states)
+// and without duplicates inside a table (the host checked)
+struct SparseImportParams {
+  void* q;               // the first table of the launch
+  size_t n_states;
+  int n_actions, count;
+  long long total;
+  const long long* base; // [count] exclusive scan of the tables' row counts
+  const int32_t* rows;   // [total]
+  const void* vals;      // [total][n_actions] in the host dtype
+};
+hipError_t launch_sparse_import(const SparseImportParams& p, int q_dtype, int host_dtype, hipStream_t stream);
 hipError_t launch_apply_delta(void* q, long long* qdelta, size_t n, int q_dtype, hipStream_t stream);
 hipError_t launch_fold_delta(long long* qdelta, size_t n, hipStream_t stream);
 hipError_t launch_battery_seq(int agents, int steps, const double* bal, double* out_bal, double* soc_hist,

@@ -19,6 +19,7 @@
 
 #include "p2pmg_internal.h"
 #include "p2pmg_plan.h"
+#include "p2pmg_sparse.h"
 
 using p2pmg::EpisodeParams;
 using p2pmg::EpisodePlan;
@@ -166,7 +167,14 @@ struct p2pmg_ctx : p2pmg::PlanFacts {
   DevBuf<double> td_part, td_out;
   DevBuf<long long> td_cpart, td_cout;
   DevBuf<uint8_t> policy_snap;
-  DevBuf<float4> hp_lv;      // [A] per-agent heat-pump levels
+  // the sparse table checkpoints (p2pmg_get_q_sparse & co.): block counts / offsets, per-table totals and
+  // bases of the last call, and the staging of one run (at most P2PMG_SPARSE_STAGE_BYTES, unless one
+  // table alone holds more); all allocated on first use
+  DevBuf<uint32_t> sp_blk;
+  DevBuf<long long> sp_total, sp_base;
+  DevBuf<int32_t> sp_rows;
+  DevBuf<char> sp_vals;
+  DevBuf<float4> hp_lv;     // [A] per-agent heat-pump levels
   DevBuf<float4> thermal;    // [A] per-agent {setpoint, lower bound, upper bound, COP} (p2pmg_set_thermal)
   DevBuf<p2pmg::LearnRow> learn;  // [A] per-agent {alpha, gamma, comfort weight} (p2pmg_set_learning)
   std::vector<p2pmg::LearnRow> h_learn;  // its host copy (p2pmg_get_learning, partial updates)
@@ -765,6 +773,162 @@ int p2pmg_policy_changes(p2pmg_ctx* c, int first, int count, int64_t* changed, i
     changed[k] = host[2 * (size_t)k];
     if (newly_visited) newly_visited[k] = host[2 * (size_t)k + 1];
   }
+  return P2PMG_OK;
+}
+
+// ---- sparse table checkpoints: the stored rows of tables [first, first + count) compacted on the device
+// (count, offset and scatter passes of p2pmg_tables.hip), imported by a scatter, and one table copied
+// over many.  Each returns `count == 0` before the device is reached.
+static_assert(sizeof(long long) == sizeof(int64_t), "per-table totals travel as int64");
+
+static int sparse_range(p2pmg_ctx* c, int first, int count, const char* what) {
+  RC_TRY(digest_range(c, first, count, what));
+  if (c->n_states > 0x7FFFFFFFull)
+    return fail(c, P2PMG_E_UNSUPPORTED, std::string(what) + ": row indices are int32 (n_states > 2^31 - 1)");
+  return P2PMG_OK;
+}
+
+static char* table_ptr(p2pmg_ctx* c, size_t table) {
+  return static_cast<char*>(c->q.get()) + table * c->n_states * kQPad * c->q_elem;
+}
+
+// the count and offset passes over the range; n_rows[count] on the host, *p what the scatter continues with
+static int sparse_count_pass(p2pmg_ctx* c, int first, int count, int64_t* n_rows, p2pmg::SparseParams* p) {
+  *p = p2pmg::SparseParams{};
+  p->q = table_ptr(c, (size_t)first);
+  p->n_states = c->n_states;
+  p->n_actions = c->cfg.n_actions;
+  p->count = count;
+  p2pmg::sparse_blocks(count, c->n_states, &p->bpt, &p->rpb);
+  HIP_TRY(c, c->sp_blk.grow((size_t)count * p->bpt));
+  HIP_TRY(c, c->sp_total.grow((size_t)count));
+  p->blk = c->sp_blk;
+  p->total = c->sp_total;
+  HIP_TRY(c, p2pmg::launch_sparse_count(*p, c->cfg.q_dtype, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(n_rows, c->sp_total, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return P2PMG_OK;
+}
+
+// staging for the largest run, and every table's base inside its own run on the device
+static int sparse_stage(p2pmg_ctx* c, const std::vector<p2pmg::SparseRun>& runs, const int64_t* n_rows, int count,
+                        size_t val_bytes) {
+  int64_t most = 0;
+  std::vector<long long> base((size_t)count);
+  for (const p2pmg::SparseRun& r : runs) {
+    most = std::max(most, r.rows);
+    long long at = 0;
+    for (int k = r.first; k < r.first + r.count; ++k) base[(size_t)k] = at, at += n_rows[k];
+  }
+  HIP_TRY(c, c->sp_rows.grow((size_t)most));
+  HIP_TRY(c, c->sp_vals.grow((size_t)most * val_bytes));
+  HIP_TRY(c, c->sp_base.grow((size_t)count));
+  HIP_TRY(c, hipMemcpyAsync(c->sp_base, base.data(), base.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // `base` goes out of scope
+  return P2PMG_OK;
+}
+
+int p2pmg_sparse_count(p2pmg_ctx* c, int first, int count, int64_t* n_rows) {
+  RC_TRY(sparse_range(c, first, count, "sparse_count"));
+  if (count == 0) return P2PMG_OK;
+  if (!n_rows) return fail(c, P2PMG_E_INVALID, "sparse_count: null output");
+  p2pmg::SparseParams p;
+  return sparse_count_pass(c, first, count, n_rows, &p);
+}
+
+int p2pmg_get_q_sparse(p2pmg_ctx* c, int first, int count, int64_t capacity, int64_t* n_rows, int32_t* rows, void* values,
+                       int host_dtype) {
+  RC_TRY(sparse_range(c, first, count, "get_q_sparse"));
+  if (count == 0) return P2PMG_OK;
+  if (!n_rows || (host_dtype != P2PMG_Q_F64 && host_dtype != P2PMG_Q_F32))
+    return fail(c, P2PMG_E_INVALID, "get_q_sparse: null n_rows or bad dtype");
+  p2pmg::SparseParams p;
+  RC_TRY(sparse_count_pass(c, first, count, n_rows, &p));
+  int64_t total = 0;
+  for (int k = 0; k < count; ++k) total += n_rows[k];
+  if (total > capacity)
+    return fail(c, P2PMG_E_INVALID, "get_q_sparse: " + std::to_string(total) + " stored rows exceed the capacity " +
+                                        std::to_string(capacity) + " (n_rows is filled)");
+  if (total == 0) return P2PMG_OK;
+  if (!rows || !values) return fail(c, P2PMG_E_INVALID, "get_q_sparse: null output");
+  const size_t val_bytes = p2pmg::sparse_row_bytes(p.n_actions, host_dtype) - sizeof(int32_t);
+  const std::vector<p2pmg::SparseRun> runs =
+      p2pmg::sparse_plan_runs(n_rows, count, p2pmg::sparse_row_bytes(p.n_actions, host_dtype), P2PMG_SPARSE_STAGE_BYTES);
+  RC_TRY(sparse_stage(c, runs, n_rows, count, val_bytes));
+  p.out_rows = c->sp_rows;
+  p.out_vals = c->sp_vals;
+  for (const p2pmg::SparseRun& r : runs) {
+    if (r.rows == 0) continue;
+    p2pmg::SparseParams pr = p;
+    pr.q = table_ptr(c, (size_t)first + (size_t)r.first);
+    pr.count = r.count;
+    pr.blk = c->sp_blk.get() + (size_t)r.first * p.bpt;
+    pr.base = c->sp_base.get() + r.first;
+    HIP_TRY(c, p2pmg::launch_sparse_scatter(pr, c->cfg.q_dtype, host_dtype, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(rows + r.row0, c->sp_rows, (size_t)r.rows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(static_cast<char*>(values) + (size_t)r.row0 * val_bytes, c->sp_vals, (size_t)r.rows * val_bytes,
+                              hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the next run reuses the staging
+  }
+  return P2PMG_OK;
+}
+
+int p2pmg_set_q_sparse(p2pmg_ctx* c, int first, int count, const int64_t* n_rows, const int32_t* rows, const void* values,
+                       int host_dtype, int zero_first) {
+  RC_TRY(sparse_range(c, first, count, "set_q_sparse"));
+  if (count == 0) return P2PMG_OK;
+  if (!n_rows || (host_dtype != P2PMG_Q_F64 && host_dtype != P2PMG_Q_F32))
+    return fail(c, P2PMG_E_INVALID, "set_q_sparse: null n_rows or bad dtype");
+  int64_t total = 0;
+  if (const char* bad = p2pmg::sparse_validate(n_rows, rows, count, c->n_states, &total))
+    return fail(c, P2PMG_E_INVALID, std::string("set_q_sparse: ") + bad);
+  if (total > 0 && !values) return fail(c, P2PMG_E_INVALID, "set_q_sparse: null values");
+  if (zero_first)
+    HIP_TRY(c, hipMemsetAsync(table_ptr(c, (size_t)first), 0, (size_t)count * c->n_states * kQPad * c->q_elem, c->stream));
+  if (total > 0) {
+    const int na = c->cfg.n_actions;
+    const size_t val_bytes = p2pmg::sparse_row_bytes(na, host_dtype) - sizeof(int32_t);
+    const std::vector<p2pmg::SparseRun> runs =
+        p2pmg::sparse_plan_runs(n_rows, count, p2pmg::sparse_row_bytes(na, host_dtype), P2PMG_SPARSE_STAGE_BYTES);
+    RC_TRY(sparse_stage(c, runs, n_rows, count, val_bytes));
+    for (const p2pmg::SparseRun& r : runs) {
+      if (r.rows == 0) continue;
+      HIP_TRY(c, hipMemcpyAsync(c->sp_rows, rows + r.row0, (size_t)r.rows * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(c->sp_vals, static_cast<const char*>(values) + (size_t)r.row0 * val_bytes,
+                                (size_t)r.rows * val_bytes, hipMemcpyHostToDevice, c->stream));
+      p2pmg::SparseImportParams ip{};
+      ip.q = table_ptr(c, (size_t)first + (size_t)r.first);
+      ip.n_states = c->n_states;
+      ip.n_actions = na;
+      ip.count = r.count;
+      ip.total = r.rows;
+      ip.base = c->sp_base.get() + r.first;
+      ip.rows = c->sp_rows;
+      ip.vals = c->sp_vals;
+      HIP_TRY(c, p2pmg::launch_sparse_import(ip, c->cfg.q_dtype, host_dtype, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));  // the next run reuses the staging
+    }
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return P2PMG_OK;
+}
+
+int p2pmg_copy_q(p2pmg_ctx* c, int src, int dst_first, int dst_count) {
+  RC_TRY(sparse_range(c, dst_first, dst_count, "copy_q"));
+  if (dst_count == 0) return P2PMG_OK;
+  if (src < 0 || (size_t)src >= c->n_tables || (src >= dst_first && src < dst_first + dst_count))
+    return fail(c, P2PMG_E_INVALID, "copy_q: the source is no table, or lies inside the destination range");
+  // the source over the first destination, then the copies made so far over as many more: ceil(log2
+  // (dst_count)) + 1 device-to-device copies, each one contiguous run of whole tables
+  const size_t bytes = c->n_states * kQPad * c->q_elem;
+  char* dst = table_ptr(c, (size_t)dst_first);
+  HIP_TRY(c, hipMemcpyAsync(dst, table_ptr(c, (size_t)src), bytes, hipMemcpyDeviceToDevice, c->stream));
+  for (size_t done = 1; done < (size_t)dst_count;) {
+    const size_t k = std::min(done, (size_t)dst_count - done);
+    HIP_TRY(c, hipMemcpyAsync(dst + done * bytes, dst, k * bytes, hipMemcpyDeviceToDevice, c->stream));
+    done += k;
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return P2PMG_OK;
 }
 

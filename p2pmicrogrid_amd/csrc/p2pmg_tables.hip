@@ -20,6 +20,9 @@
 // Every result is a count, a minimum or a maximum, so none depends on the grid shape or on any order;
 // zero extrema are returned as +0.0.  Padding columns (k >= n_actions) are loaded with the row and never
 // used.
+// The sparse table checkpoints (p2pmg_sparse_count, p2pmg_get_q_sparse, p2pmg_set_q_sparse) follow the
+// digest below: the same loads, a count / offset / scatter triple for the export and a one-thread-per-row
+// import.
 #include "p2pmg_internal.h"
 
 namespace p2pmg {
@@ -241,7 +244,211 @@ void launch_typed(const TableDigestParams& p, hipStream_t stream) {
   }
 }
 
+// ---- sparse table checkpoints (p2pmg_sparse_count, p2pmg_get_q_sparse, p2pmg_set_q_sparse): the same
+// streaming loads as the digest.  Block b of a table owns its rows [b * rpb, (b + 1) * rpb), rpb a multiple
+// of kTile, so that the row order is (block, loop trip, u, wave, lane) and a row's place in the output
+// is a sum of counts taken in that order.
+//   sparse_count_kernel<QT>       stored rows of the block: popcounts of wave ballots -> LDS -> blk[block]
+//   sparse_offset_kernel          one wave per table: ordered exclusive scan of the table's bpt block
+//                                 counts in place, and the table's total
+//   sparse_scatter_kernel<QT, D>  the count pass again; per loop trip the kUnroll x kWaves ballot counts
+//                                 go through LDS (double-buffered: one barrier per trip), and a stored row
+//                                 lands at base[table] + blk[block] + rows of earlier trips + counts of
+//                                 the (u, wave) pairs before its own + its rank in the wave's ballot (mbcnt)
+//   sparse_import_kernel<QT, S>   one thread per listed row writes one padded row
+// No atomics anywhere: the output bytes do not depend on the grid.
+constexpr unsigned kSparseTiles = 4;  // a block's rows: at most this many tiles
+
+__device__ __forceinline__ bool nonzero_bits(double x) { return __double_as_longlong(x) != 0; }
+__device__ __forceinline__ bool nonzero_bits(float x) { return __float_as_uint(x) != 0u; }
+// -0.0 counts: storedness is a matter of bits, not of value
+template <typename QT>
+__device__ __forceinline__ bool row_stored(const Row<QT>& x, int na) {
+  bool s = nonzero_bits(x.v[0]);
+#pragma unroll
+  for (int k = 1; k < kQPad; ++k) s = s || (k < na && nonzero_bits(x.v[k]));
+  return s;
+}
+
+template <typename QT>
+__global__ __launch_bounds__(kBlock) void sparse_count_kernel(const SparseParams p) {
+  const unsigned tbl = blockIdx.x / p.bpt, blk = blockIdx.x - tbl * p.bpt;
+  const size_t n = p.n_states;
+  const QT* q = reinterpret_cast<const QT*>(p.q) + (size_t)tbl * n * kQPad;
+  const size_t begin = (size_t)blk * p.rpb, end = begin + p.rpb < n ? begin + p.rpb : n;
+  unsigned cnt = 0;  // wave-uniform
+  for (size_t r0 = begin; r0 < end; r0 += kTile) {
+    Row<QT> row[kUnroll];
+    // rows past the table's end re-read its last row (in bounds) and count nowhere
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const size_t r = r0 + (size_t)u * kBlock + threadIdx.x;
+      row[u] = load_row(q, r < n ? r : n - 1);
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const size_t r = r0 + (size_t)u * kBlock + threadIdx.x;
+      cnt += (unsigned)__popcll(__ballot(r < n && row_stored(row[u], p.n_actions)));
+    }
+  }
+  __shared__ unsigned s_cnt[kWaves];
+  if ((threadIdx.x & (kWave - 1)) == 0) s_cnt[threadIdx.x / kWave] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned c = s_cnt[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) c += s_cnt[w];
+    p.blk[blockIdx.x] = c;
+  }
+}
+
+__global__ __launch_bounds__(kWave) void sparse_offset_kernel(const SparseParams p) {
+  uint32_t* c = p.blk + (size_t)blockIdx.x * p.bpt;
+  const unsigned lane = threadIdx.x;
+  unsigned run = 0;  // stored rows of the blocks before this trip's 64
+  for (unsigned b0 = 0; b0 < p.bpt; b0 += kWave) {
+    const unsigned b = b0 + lane;
+    const unsigned v = b < p.bpt ? c[b] : 0u;
+    unsigned inc = v;  // inclusive scan across the wave
+#pragma unroll
+    for (int m = 1; m < kWave; m <<= 1) {
+      const unsigned t = __shfl_up(inc, m);
+      if (lane >= (unsigned)m) inc += t;
+    }
+    if (b < p.bpt) c[b] = run + inc - v;
+    run += __shfl(inc, kWave - 1);
+  }
+  if (lane == 0) p.total[blockIdx.x] = (long long)run;
+}
+
+template <typename QT, typename D>
+__global__ __launch_bounds__(kBlock) void sparse_scatter_kernel(const SparseParams p) {
+  const unsigned tbl = blockIdx.x / p.bpt, blk = blockIdx.x - tbl * p.bpt;
+  const size_t n = p.n_states;
+  const int na = p.n_actions;
+  const QT* q = reinterpret_cast<const QT*>(p.q) + (size_t)tbl * n * kQPad;
+  D* vals = reinterpret_cast<D*>(p.out_vals);
+  const size_t begin = (size_t)blk * p.rpb, end = begin + p.rpb < n ? begin + p.rpb : n;
+  const unsigned lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  size_t pos = (size_t)p.base[tbl] + p.blk[blockIdx.x];  // where this trip's first stored row goes
+  // a trip writes half `buf`, the barrier, then reads it; the next trip uses the other half, and nobody
+  // reaches the trip after that (this half again) before every wave has passed the next trip's barrier
+  __shared__ unsigned s_w[2][kUnroll * kWaves];
+  int buf = 0;
+  for (size_t r0 = begin; r0 < end; r0 += kTile, buf ^= 1) {
+    Row<QT> row[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const size_t r = r0 + (size_t)u * kBlock + threadIdx.x;
+      row[u] = load_row(q, r < n ? r : n - 1);
+    }
+    unsigned long long bal[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const size_t r = r0 + (size_t)u * kBlock + threadIdx.x;
+      bal[u] = __ballot(r < n && row_stored(row[u], na));
+      if (lane == 0) s_w[buf][u * kWaves + wave] = (unsigned)__popcll(bal[u]);
+    }
+    __syncthreads();
+    unsigned acc = 0;  // stored rows of the trip before (u, wave 0)
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      unsigned mine = acc;
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) {
+        const unsigned c = s_w[buf][u * kWaves + w];
+        if ((unsigned)w < wave) mine += c;
+        acc += c;
+      }
+      if ((bal[u] >> lane) & 1ull) {
+        const unsigned rank =
+            __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[u], 0u));
+        const size_t at = pos + mine + rank;
+        p.out_rows[at] = (int32_t)(r0 + (size_t)u * kBlock + threadIdx.x);
+#pragma unroll
+        for (int k = 0; k < kQPad; ++k)
+          if (k < na) vals[at * (size_t)na + k] = (D)row[u].v[k];
+      }
+    }
+    pos += acc;
+  }
+}
+
+__device__ __forceinline__ void store_row(double* q, size_t r, const double (&v)[kQPad]) {
+  double2* d = reinterpret_cast<double2*>(q) + 2 * r;
+  d[0] = make_double2(v[0], v[1]);
+  d[1] = make_double2(v[2], v[3]);
+}
+__device__ __forceinline__ void store_row(float* q, size_t r, const float (&v)[kQPad]) {
+  reinterpret_cast<float4*>(q)[r] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+template <typename QT, typename S>
+__global__ __launch_bounds__(kBlock) void sparse_import_kernel(const SparseImportParams p) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= p.total) return;
+  int lo = 0, hi = p.count;  // base[lo] <= i < base[hi], base[count] = total
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (p.base[mid] <= i) lo = mid;
+    else hi = mid;
+  }
+  const S* src = reinterpret_cast<const S*>(p.vals) + (size_t)i * p.n_actions;
+  QT v[kQPad];
+#pragma unroll
+  for (int k = 0; k < kQPad; ++k) v[k] = k < p.n_actions ? (QT)src[k] : (QT)0;
+  store_row(reinterpret_cast<QT*>(p.q), (size_t)lo * p.n_states + (size_t)p.rows[i], v);
+}
+
+bool sparse_params_ok(const SparseParams& p) {
+  return p.bpt != 0 && p.rpb != 0 && p.rpb % kTile == 0 && (size_t)p.bpt * p.rpb >= p.n_states && p.n_actions >= 1 &&
+         p.n_actions <= kQPad && p.blk && (size_t)p.count * p.bpt <= 0x7FFFFFFFull;
+}
+
 }  // namespace
+
+void sparse_blocks(int count, size_t n_states, unsigned* bpt, unsigned* rpb) {
+  const size_t tiles = n_states ? (n_states + kTile - 1) / kTile : 1;
+  // whole tiles per block: one while the tables give fewer than kTargetBlocks blocks, then up to kSparseTiles
+  size_t tpb = tiles * (size_t)(count > 0 ? count : 1) / kTargetBlocks;
+  tpb = tpb < 1 ? 1 : (tpb > kSparseTiles ? kSparseTiles : tpb);
+  *rpb = (unsigned)tpb * kTile;
+  *bpt = (unsigned)((tiles + tpb - 1) / tpb);
+}
+
+hipError_t launch_sparse_count(const SparseParams& p, int q_dtype, hipStream_t stream) {
+  if (p.count <= 0 || p.n_states == 0) return hipSuccess;
+  if (!sparse_params_ok(p) || !p.total) return hipErrorInvalidValue;
+  const dim3 g((unsigned)p.count * p.bpt), b(kBlock);
+  if (q_dtype == 0) hipLaunchKernelGGL(sparse_count_kernel<double>, g, b, 0, stream, p);
+  else hipLaunchKernelGGL(sparse_count_kernel<float>, g, b, 0, stream, p);
+  hipLaunchKernelGGL(sparse_offset_kernel, dim3((unsigned)p.count), dim3(kWave), 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_sparse_scatter(const SparseParams& p, int q_dtype, int host_dtype, hipStream_t stream) {
+  if (p.count <= 0 || p.n_states == 0) return hipSuccess;
+  if (!sparse_params_ok(p) || !p.base || !p.out_rows || !p.out_vals) return hipErrorInvalidValue;
+  const dim3 g((unsigned)p.count * p.bpt), b(kBlock);
+  if (q_dtype == 0 && host_dtype == 0) hipLaunchKernelGGL((sparse_scatter_kernel<double, double>), g, b, 0, stream, p);
+  else if (q_dtype == 0) hipLaunchKernelGGL((sparse_scatter_kernel<double, float>), g, b, 0, stream, p);
+  else if (host_dtype == 0) hipLaunchKernelGGL((sparse_scatter_kernel<float, double>), g, b, 0, stream, p);
+  else hipLaunchKernelGGL((sparse_scatter_kernel<float, float>), g, b, 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_sparse_import(const SparseImportParams& p, int q_dtype, int host_dtype, hipStream_t stream) {
+  if (p.count <= 0 || p.total <= 0) return hipSuccess;
+  const long long blocks = (p.total + kBlock - 1) / kBlock;
+  if (!p.q || !p.base || !p.rows || !p.vals || p.n_actions < 1 || p.n_actions > kQPad || blocks > 0x7FFFFFFFll)
+    return hipErrorInvalidValue;
+  const dim3 g((unsigned)blocks), b(kBlock);
+  if (q_dtype == 0 && host_dtype == 0) hipLaunchKernelGGL((sparse_import_kernel<double, double>), g, b, 0, stream, p);
+  else if (q_dtype == 0) hipLaunchKernelGGL((sparse_import_kernel<double, float>), g, b, 0, stream, p);
+  else if (host_dtype == 0) hipLaunchKernelGGL((sparse_import_kernel<float, double>), g, b, 0, stream, p);
+  else hipLaunchKernelGGL((sparse_import_kernel<float, float>), g, b, 0, stream, p);
+  return hipGetLastError();
+}
 
 unsigned table_digest_blocks(int count, size_t n_states) {
   if (count <= 0 || n_states == 0) return 1;

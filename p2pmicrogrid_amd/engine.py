@@ -209,6 +209,77 @@ class DeviceCommunityBatch:
                                               int(bool(remark))), "policy_changes")
         return {"changed": ch, "newly_visited": nv}
 
+    # ----------------------------------------------------------------- sparse table checkpoints
+    def sparse_count(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """int64 [count]: the stored rows of tables [first, first + count), rows with a non-zero bit in
+        one of their n_actions entries (p2pmg_sparse_count; -0.0 counts, unlike table_stats' visited)."""
+        first, count = self._table_range(first, count)
+        out = np.zeros(max(count, 0), np.int64)
+        self._chk(self.L.p2pmg_sparse_count(self._ctx, first, count, out.ctypes.data), "sparse_count")
+        return out
+
+    def get_q_sparse(self, first: int = 0, count: Optional[int] = None, dtype=None) -> Dict[str, np.ndarray]:
+        """The sparse form of tables [first, first + count), compacted on the device (p2pmg_get_q_sparse):
+        {"shape": q_shape int64 [5], "offsets": int64 [count + 1], "rows": int32 [total] state indices of the
+        stored rows, ascending inside each table, "values": [total, n_actions]}; table k's rows are
+        rows[offsets[k]:offsets[k + 1]].  dtype None: the tables' own (then bit for bit)."""
+        first, count = self._table_range(first, count)
+        dt = np.dtype((np.float64 if self.q_dtype == "f64" else np.float32) if dtype is None else dtype)
+        if dt not in (np.float64, np.float32):
+            raise ValueError(f"dtype must be float64 or float32, got {dt}")
+        n_rows = self.sparse_count(first, count)
+        total = int(n_rows.sum())
+        rows = np.empty(total, np.int32)
+        values = np.empty((total, self.q_shape[-1]), dt)
+        self._chk(self.L.p2pmg_get_q_sparse(self._ctx, first, count, total, n_rows.ctypes.data, rows.ctypes.data,
+                                            values.ctypes.data, _lib.Q_F64 if dt == np.float64 else _lib.Q_F32),
+                  "get_q_sparse")
+        offsets = np.zeros(max(count, 0) + 1, np.int64)
+        np.cumsum(n_rows, out=offsets[1:])
+        return {"shape": np.asarray(self.q_shape, np.int64), "offsets": offsets, "rows": rows, "values": values}
+
+    def set_q_sparse(self, sparse, first: int = 0, zero: bool = True):
+        """Write a sparse form's tables over tables [first, first + its count) by a scatter on the device
+        (p2pmg_set_q_sparse).  zero: those tables are zeroed first, so that they become the form's tables;
+        else only the listed rows are overwritten.  ValueError for a form of another table shape; what the
+        library refuses (unsorted, duplicated or out-of-range indices) leaves the tables unchanged."""
+        from .rl import SPARSE_KEYS
+        missing = [k for k in SPARSE_KEYS if k not in sparse]
+        if missing:
+            raise ValueError(f"not a sparse table form: no {missing}")
+        shape = tuple(int(x) for x in np.asarray(sparse["shape"]).reshape(-1))
+        if shape != tuple(self.q_shape):
+            raise ValueError(f"sparse form holds tables of shape {shape}, this context {tuple(self.q_shape)}")
+        offsets = np.ascontiguousarray(sparse["offsets"], np.int64).reshape(-1)
+        rows = np.ascontiguousarray(sparse["rows"], np.int32).reshape(-1)
+        values = np.asarray(sparse["values"])
+        values = np.ascontiguousarray(values, values.dtype if values.dtype in (np.float64, np.float32) else np.float64)
+        if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != rows.size or values.shape != (rows.size, shape[-1]):
+            raise ValueError("sparse form: offsets, rows and values do not belong together")
+        n_rows = np.ascontiguousarray(np.diff(offsets))
+        code = _lib.Q_F64 if values.dtype == np.float64 else _lib.Q_F32
+        self._chk(self.L.p2pmg_set_q_sparse(self._ctx, int(first), n_rows.size, n_rows.ctypes.data, rows.ctypes.data,
+                                            values.ctypes.data, code, int(bool(zero))), "set_q_sparse")
+
+    def copy_q(self, src: int, first: int, count: int):
+        """Tables [first, first + count) become bit copies of table src, on the device (p2pmg_copy_q)."""
+        self._chk(self.L.p2pmg_copy_q(self._ctx, int(src), int(first), int(count)), "copy_q")
+
+    def save_tables(self, path: str, first: int = 0, count: Optional[int] = None) -> str:
+        """Tables [first, first + count) as one uncompressed .npz with the four keys of get_q_sparse, in
+        the tables' own dtype; returns the path written (".npz" appended where missing)."""
+        from .rl import save_sparse_file
+        return save_sparse_file(path, self.get_q_sparse(first, count))
+
+    def load_tables(self, path: str, first: int = 0) -> int:
+        """The tables of a save_tables file over tables [first, first + its count) (np.load with
+        allow_pickle=False); ValueError where the file's table shape is not this context's.  Returns
+        the number of tables loaded."""
+        from .rl import load_sparse_file
+        sparse = load_sparse_file(path, self.q_shape)
+        self.set_q_sparse(sparse, first=first, zero=True)
+        return int(sparse["offsets"].size - 1)
+
     # ----------------------------------------------------------------- heterogeneous agents / storage
     def set_hp_levels(self, levels):
         """Per-agent heat-pump power of actions 0..2 in W, [S, N, 3] (0 for agents without one)."""

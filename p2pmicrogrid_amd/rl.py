@@ -5,7 +5,8 @@ inside a ``CommunityMicrogrid`` it is the agent's slot of the community's device
 (the episode kernel reads and updates it); a standalone actor owns a private one-agent device
 context.  ``q_table`` / ``set_qtable`` copy to / from the reference layout
 (n_time, n_temp, n_balance, n_p2p, n_actions) float64, and ``load_from_file`` /
-``save_to_file`` read / write the reference's ``.npy`` checkpoints (rl.py:83-87).
+``save_to_file`` read / write the reference's ``.npy`` checkpoints (rl.py:83-87);
+``save_sparse`` / ``load_sparse`` the sparse ``.npz`` form (``sparse_table`` states the format).
 Per-call ``select_action`` / ``greedy_action`` / ``train`` run on the device (p2pmg_q_calls);
 the exploration draws use the global np.random exactly as rl.py:101-111 does.
 """
@@ -45,6 +46,94 @@ def table_digest(q_table: np.ndarray) -> Tuple[np.ndarray, dict]:
              "abs_max": np.float64(max(-lo, hi)) + 0.0,
              "greedy": np.array([(visited & (greedy == k)).sum() for k in range(na)], np.int64)}
     return np.where(visited, greedy, np.uint8(255)).astype(np.uint8), stats
+
+
+SPARSE_KEYS = ("shape", "offsets", "rows", "values")
+
+
+def _bits(x: np.ndarray) -> np.ndarray:
+    return x.view(np.uint64 if x.dtype == np.float64 else np.uint32)
+
+
+def sparse_table(q_table: np.ndarray) -> dict:
+    """The sparse form of include/p2pmg.h on the host: one table (n_time, n_temp, n_balance, n_p2p,
+    n_actions), or tables [count, ...] (six axes), f64 or f32 (anything else is taken as f64) ->
+    {"shape": the table shape int64 [5], "offsets": int64 [count + 1], "rows": int32 [total], "values":
+    [total, n_actions]}.  A row is stored iff one of its entries has a non-zero BIT pattern (-0.0
+    counts); rows holds the state indices of the stored rows, table after table (table k's are
+    rows[offsets[k]:offsets[k + 1]]), ascending inside each table; values their entries, same order."""
+    q = np.asarray(q_table)
+    if q.dtype not in (np.float64, np.float32):
+        q = q.astype(np.float64)
+    if q.ndim not in (5, 6):
+        raise ValueError(f"one table (5 axes) or [count, ...] tables (6 axes), got shape {q.shape}")
+    shape = q.shape[-5:]
+    flat = np.ascontiguousarray(q).reshape(-1, int(np.prod(shape[:-1])), shape[-1])
+    if flat.shape[1] > 2 ** 31 - 1:
+        raise ValueError("row indices are int32: at most 2^31 - 1 states")
+    table, row = np.nonzero((_bits(flat) != 0).any(axis=-1))  # row-major: by table, then ascending row
+    offsets = np.zeros(flat.shape[0] + 1, np.int64)
+    np.cumsum(np.bincount(table, minlength=flat.shape[0]), out=offsets[1:])
+    return {"shape": np.asarray(shape, np.int64), "offsets": offsets, "rows": row.astype(np.int32),
+            "values": flat[table, row]}
+
+
+def check_sparse(sparse, shape=None) -> Tuple[tuple, np.ndarray, np.ndarray, np.ndarray]:
+    """(shape, offsets int64, rows int32, values f64 | f32) of a sparse form, or ValueError where it is
+    none: keys, array shapes, offsets from 0 to len(rows) without a step back or one above n_states, every
+    index in [0, n_states) and strictly ascending inside its table; shape: the table shape it must have."""
+    missing = [k for k in SPARSE_KEYS if k not in sparse]
+    if missing:
+        raise ValueError(f"not a sparse table form: no {missing}")
+    shp = tuple(int(x) for x in np.asarray(sparse["shape"]).reshape(-1))
+    if len(shp) != 5 or min(shp) < 1:
+        raise ValueError(f"sparse form: bad table shape {shp}")
+    if shape is not None and shp != tuple(shape):
+        raise ValueError(f"sparse form holds tables of shape {shp}, not {tuple(shape)}")
+    offsets = np.ascontiguousarray(sparse["offsets"], np.int64).reshape(-1)
+    rows = np.ascontiguousarray(sparse["rows"], np.int32).reshape(-1)
+    values = np.asarray(sparse["values"])
+    values = np.ascontiguousarray(values, values.dtype if values.dtype in (np.float64, np.float32) else np.float64)
+    n_states = int(np.prod(shp[:-1]))
+    steps = np.diff(offsets)
+    if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (steps < 0).any() or (steps > n_states).any():
+        raise ValueError("sparse form: offsets do not run from 0 to len(rows) in steps within [0, n_states]")
+    if values.shape != (rows.size, shp[-1]):
+        raise ValueError(f"sparse form: values {values.shape} for {rows.size} rows of {shp[-1]} actions")
+    if rows.size and (rows.min() < 0 or rows.max() >= n_states):
+        raise ValueError("sparse form: row index outside [0, n_states)")
+    starts = np.zeros(rows.size, bool)
+    starts[offsets[:-1][steps > 0]] = True  # the first index of a table need not exceed the one before it
+    if rows.size and (np.diff(rows.astype(np.int64)) <= 0)[~starts[1:]].any():
+        raise ValueError("sparse form: row indices not strictly ascending inside a table")
+    return shp, offsets, rows, values
+
+
+def dense_table(sparse) -> np.ndarray:
+    """[count, *shape] in the dtype of ``values``: zeros (+0.0), then the stored rows written.
+    ``dense_table(sparse_table(q))`` has q's bytes, except that it always has the leading count axis."""
+    shp, offsets, rows, values = check_sparse(sparse)
+    count = offsets.size - 1
+    out = np.zeros((count, int(np.prod(shp[:-1])), shp[-1]), values.dtype)
+    out[np.repeat(np.arange(count), np.diff(offsets)), rows] = values
+    return out.reshape(count, *shp)
+
+
+def save_sparse_file(path: str, sparse) -> str:
+    """One uncompressed .npz with exactly the four keys of the sparse form; returns the path written."""
+    shp, offsets, rows, values = check_sparse(sparse)
+    path = path if path.endswith(".npz") else path + ".npz"
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    np.savez(path, shape=np.asarray(shp, np.int64), offsets=offsets, rows=rows, values=values)
+    return path
+
+
+def load_sparse_file(path: str, shape=None) -> dict:
+    """The sparse form a file holds (allow_pickle=False), checked; ValueError where it is none or where its
+    tables are not of ``shape``."""
+    with np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False) as f:
+        shp, offsets, rows, values = check_sparse({k: f[k] for k in f.files}, shape)
+    return {"shape": np.asarray(shp, np.int64), "offsets": offsets, "rows": rows, "values": values}
 
 
 class ActorInterface(ABC):
@@ -152,6 +241,25 @@ class QActor(ActorInterface):
         d = os.path.join(MODELS_DIR, f"models_{implementation}")
         os.makedirs(d, exist_ok=True)
         np.save(os.path.join(d, f"{setting}.npy"), self.q_table)
+
+    def save_sparse(self, path: str) -> None:
+        """This actor's table as a sparse checkpoint (one table: the .npz of save_sparse_file, the format
+        of DeviceCommunityBatch.save_tables).  Bound: compacted on the device (p2pmg_get_q_sparse), so
+        only the stored rows travel."""
+        if self._engine is None:
+            save_sparse_file(path, sparse_table(self.q_table))
+        else:
+            self._engine.save_tables(path, first=self._slot, count=1)
+
+    def load_sparse(self, path: str) -> None:
+        """Replace the table by a one-table sparse checkpoint's (every row it does not list becomes zero)."""
+        sparse = load_sparse_file(path, self._shape)
+        if sparse["offsets"].size != 2:
+            raise ValueError(f"{path} holds {sparse['offsets'].size - 1} tables, an actor has one")
+        if self._engine is None:
+            self._host_table = dense_table(sparse)[0].astype(np.float64)
+        else:
+            self._engine.set_q_sparse(sparse, first=self._slot, zero=True)
 
     # ------------------------------------------------------------ per-call API (rl.py:89-132)
     def _get_state_indices(self, state) -> Tuple[int, int, int, int]:
