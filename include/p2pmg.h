@@ -161,7 +161,9 @@ typedef struct p2pmg_episode_args {
 
 /* Philox placement: a parallel pre-pass writing per-step code words (latency-bound batches:
  * the episode loop only loads a prefetched word) or inline in the episode kernel (bandwidth-
- * bound batches: no extra HBM traffic).  Automatic: pre-pass below 2^18 agents.  Same stream. */
+ * bound batches: no extra HBM traffic).  Automatic: pre-pass below 2^18 agents (the shared-table
+ * N = 16 kernel: inline); either flag overrides it on the general and shared-table kernels (a pre-pass launch
+ * of the shared-table N = 16 kernel reads p2pmg_last_kernel: "...,philox-prepass...>").  Same stream. */
 #define P2PMG_FLAG_PHILOX_PREPASS 1
 #define P2PMG_FLAG_PHILOX_INKERNEL 2
 /* Kernel choice.  Automatic: the fast per-agent-table kernel (step pre-pass + rounds unrolled at

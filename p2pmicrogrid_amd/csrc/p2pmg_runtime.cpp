@@ -1121,8 +1121,21 @@ static int prepare_fast(p2pmg_ctx* c, const p2pmg_episode_args* args, const Chai
   return P2PMG_OK;
 }
 
-// The sq16 kernel: the step words {balance, time / balance row offset}, recomputed after any input upload
-static int prepare_sq16(p2pmg_ctx* c, const p2pmg_episode_args* args, EpisodeParams& p) {
+// The Philox code words of a launch whose plan draws them ahead of it (Philox::CodesPrepass): the
+// kernel then reads them like uploaded replay codes (p.rng = 0)
+static int codes_prepass(p2pmg_ctx* c, EpisodeParams& p) {
+  RC_TRY(ensure_codes(c));
+  p.codes = c->codes;
+  HIP_TRY(c, p2pmg::launch_philox_codes(p, c->codes, c->stream));
+  c->code_src = 2;
+  c->have_codes = false;  // a replay upload must be repeated after a pre-pass overwrote it
+  p.rng = 0;
+  return P2PMG_OK;
+}
+
+// The sq16 kernel: the step words {balance, time / balance row offset}, recomputed after any input upload;
+// the Philox draws in the kernel unless the caller asked for the pre-pass (P2PMG_FLAG_PHILOX_PREPASS)
+static int prepare_sq16(p2pmg_ctx* c, const p2pmg_episode_args* args, const EpisodePlan& plan, EpisodeParams& p) {
   RC_TRY(ensure_rec_pack(c, args));
   p.rec_pack = c->rec_pack;
   if (!c->sqp) HIP_TRY(c, c->sqp.alloc((size_t)c->T * c->A));
@@ -1131,7 +1144,7 @@ static int prepare_sq16(p2pmg_ctx* c, const p2pmg_episode_args* args, EpisodePar
     c->sqp_version = c->inputs_version;
   }
   p.sqp = c->sqp;
-  return P2PMG_OK;
+  return plan.philox == p2pmg::Philox::CodesPrepass ? codes_prepass(c, p) : P2PMG_OK;
 }
 
 // The general kernel (either form): unpacked record arrays, and the Philox code words where the
@@ -1139,14 +1152,7 @@ static int prepare_sq16(p2pmg_ctx* c, const p2pmg_episode_args* args, EpisodePar
 static int prepare_general(p2pmg_ctx* c, const p2pmg_episode_args* args, const EpisodePlan& plan, EpisodeParams& p) {
   RC_TRY(ensure_records(c, args->record));
   bind_records(c, p);
-  if (plan.philox != p2pmg::Philox::CodesPrepass) return P2PMG_OK;
-  RC_TRY(ensure_codes(c));
-  p.codes = c->codes;
-  HIP_TRY(c, p2pmg::launch_philox_codes(p, c->codes, c->stream));
-  c->code_src = 2;
-  c->have_codes = false;  // a replay upload must be repeated after a pre-pass overwrote it
-  p.rng = 0;
-  return P2PMG_OK;
+  return plan.philox == p2pmg::Philox::CodesPrepass ? codes_prepass(c, p) : P2PMG_OK;
 }
 
 // The hazard distance of the uploaded inputs, from the pre-pass words the launch is about to read: one
@@ -1185,7 +1191,7 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
   EpisodeParams p = episode_params(c, args);
   const int ps = c->pslot;
   p2pmg::PrepOut next{};
-  RC_TRY(fast ? prepare_fast(c, args, ch, plan, p, &next) : sq16 ? prepare_sq16(c, args, p) : prepare_general(c, args, plan, p));
+  RC_TRY(fast ? prepare_fast(c, args, ch, plan, p, &next) : sq16 ? prepare_sq16(c, args, plan, p) : prepare_general(c, args, plan, p));
   if (fast && ch && c->lag_version != c->inputs_version) {  // the first chained launch after an upload
     RC_TRY(update_chain_lag(c, c->pre[ps]));
     plan = p2pmg::plan_episode(*c, *args, true, overrides(), ch->n);  // ... with the fact it was missing
@@ -1214,6 +1220,8 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
                     std::to_string(c->N) + (tile ? ",tile" + std::to_string(p2pmg::general_tile_cap(c->N)) : "") + "," +
                     (g.q_dtype == 0 ? "f64" : "f32") + ",R1=" + std::to_string(c->R + 1) +
                     (ext ? (train ? ",train" : ",greedy") : "") + (g.shared_q ? ",shared" : "") + (c->roles ? ",roles" : "") +
+                    // sq16 draws in the kernel by default: a launch that read pre-pass code words instead says so
+                    (sq16 && plan.philox == p2pmg::Philox::CodesPrepass ? ",philox-prepass" : "") +
                     (c->battery ? (ext && !p.bat_safe ? ",battery,range-checked>" : ",battery>")
                                 : plan.interleave ? ",interleaved>" : ">"),
                 args->record, ext ? (args->record & 127) : 0, plan.rec_narrow);

@@ -113,6 +113,10 @@ int main() {
     CHECK(plan(g, greedy()).family == Family::General);
     CHECK(plan(f, train(P2PMG_RNG_PHILOX)).philox == Philox::InKernel);
     CHECK(plan(f, train(P2PMG_RNG_REPLAY)).philox == Philox::None);
+    // an explicit pre-pass request keeps the kernel and moves its draws to the code-word pre-pass
+    const EpisodePlan pp = plan(f, train(P2PMG_RNG_PHILOX, 0.81, P2PMG_FLAG_PHILOX_PREPASS));
+    CHECK(pp.family == Family::Sq16 && pp.philox == Philox::CodesPrepass && pp.packed_records);
+    CHECK(plan(f, train(P2PMG_RNG_PHILOX, 0.81, P2PMG_FLAG_PHILOX_INKERNEL)).philox == Philox::InKernel);
   }
   {  // where a general launch draws its Philox codes: the pre-pass below 2^18 agents
     const int gen = P2PMG_FLAG_GENERAL_KERNEL;
