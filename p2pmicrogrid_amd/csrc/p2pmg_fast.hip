@@ -49,9 +49,11 @@ __device__ __forceinline__ void gather_even(float ev, float (&col)[N], int i) {
 #define P2PMG_BAT_SPEC 1  // configs[3] 59.6 -> 58.7 ms (profiles/r04_battery_ab.txt)
 #endif
 // BAT: 0 none, 1 battery with per-lane range tests, 2 battery in the launcher-verified domain
-// PIPE (chained training launches, no battery; the plan's `interleave`): two chained episodes per wave.
-// Lanes 0-31 run episodes 0, 2, 4, ... of their agents and lanes 32-63 episodes 1, 3, 5, ... of the SAME
-// agents, in lockstep, half an episode (L = T / 2 steps) behind: an agent's consecutive episodes are
+// KG > 1 (PIPE; chained training launches, no battery; the plan's `groups`): KG = 2 or 4 chained episodes
+// per wave, in KG lane groups of 64 / KG lanes.  Group g runs episodes g, g + KG, g + 2 KG, ... of the SAME
+// agents as every other group, in lockstep, L = T / KG steps behind group g - 1.  What follows describes
+// KG = 2 (lanes 0-31 and 32-63, half an episode apart); the last paragraph says what KG = 4 adds.
+// An agent's consecutive episodes are
 // coupled only through its table (the later one starts from its own T0 draw), and the launcher sends
 // this form only inputs whose hazard distance keeps every conflicting pair of row accesses at least
 // four steps apart in the order of the serial chain (chain_lag_kernel).  Lockstep time runs in phases
@@ -65,7 +67,26 @@ __device__ __forceinline__ void gather_even(float ev, float (&col)[N], int i) {
 // bit is set and its own loaded row where it is clear.  The hazard rule puts every such store at least
 // four steps before the leader loads the row, and every leader store to those rows before the
 // follower's first read, so the logged value is what the serial chain reads.
-template <int N, typename QT, int R1, bool TRAIN, int BAT, bool NARROW, bool PIPE = false>
+//
+// KG = 4 (a quarter episode apart; the launcher sends T % 12 == 0 and D + 4 <= T / 4).  Episode e lives in
+// group e % 4 for its whole life; in phase ph group ph % 4 is at an episode boundary and group (ph + 1) % 4
+// in its episode's last quarter; the loop ends after phase n_chain + 2, and a group without an episode
+// (fill, drain) runs masked to the dummy slots.  Hazards: steps u of episode e and v of episode e + j run at
+// lockstep times u and j L + v.  A conflicting pair (chain_lag_kernel) has u - v <= D <= L - 4 <= j L - 4, so
+// u's access precedes v's by at least four steps for j = 1, and by more for j = 2, 3: adjacent episodes
+// decide.  The wrap row of episode e (key of step 0, bin iT of its step T - 1, p2p = 0) may by then hold
+// stores of e + 1, e + 2 (earlier phases) and e + 3 (this phase; every step on step 0's key is a step
+// v <= D <= L - 4 of its episode, so it ran before this lockstep step).  Each group keeps its own log and
+// mask for the life of its episode (reset in its own prologue), and the leader takes the value of the
+// EARLIEST follower that logged the bin: group grp + 1's, else grp + 2's, else grp + 3's, else its own
+// loaded row.  Why that is the serial value: a follower's first read of the row runs at least L >= D + 4
+// steps after the last store of every earlier episode to a row of that key (those are steps <= D of
+// episodes that began at least L steps before it), so it has seen them all; if no earlier follower stored
+// into the row, what it read is what episode e left, which is what the serial chain reads at e's step
+// T - 1 (e's own stores to the key are steps <= D of its first quarter).  If no follower logged the bin,
+// none stored into the row and the loaded row is the serial one.  Whether a follower's store has landed
+// when the row is loaded does not matter: the loaded row is used only where no follower stored at all.
+template <int N, typename QT, int R1, bool TRAIN, int BAT, bool NARROW, int KG = 1>
 __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams p, const uint2* __restrict__ pre,
                                                              FastRec* __restrict__ recs, int spw, int n_cons,
                                                              const PrepOut nxt) {
@@ -82,14 +103,18 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
   }
   constexpr int G = pow2ceil(N);
   static_assert(G <= 8 && R1 >= 1 && R1 <= 4, "fast path: G <= 8, R + 1 <= 4");
-  static_assert(!PIPE || (TRAIN && BAT == 0), "two episodes per wave: chained training launches without a battery");
+  constexpr bool PIPE = KG > 1;    // KG lane groups, each running its own episode of the chain
+  constexpr int GW = kWave / KG;   // lanes per group
+  static_assert(KG == 1 || KG == 2 || KG == 4, "lane groups per wave: 1 (off), 2 or 4");
+  static_assert(!PIPE || (TRAIN && BAT == 0), "several episodes per wave: chained training launches without a battery");
+  static_assert(!PIPE || GW % G == 0, "a scenario's lanes stay inside one group");
   // N = 2: round 1's Q row is one of three (by the partner's round-0 action) whose bins the
   // pre-pass wrote; all three are issued a step ahead, so round 1 waits for no gather
   // (not with a battery: the partner's round-0 power then depends on its state of charge)
   constexpr bool CAND = N == 2 && R1 >= 2 && BAT == 0;
   const int lane = (int)threadIdx.x;
-  const int grp = PIPE ? lane >> 5 : 0;    // PIPE: the half of the wave (even / odd episodes of the chain)
-  const int hl = PIPE ? (lane & 31) : lane;  // ... and the lane inside it: every exchange stays inside a half
+  const int grp = PIPE ? lane / GW : 0;    // PIPE: the lane group (episodes grp, grp + KG, ... of the chain)
+  const int hl = PIPE ? lane % GW : lane;  // ... and the lane inside it: every exchange stays inside a group
   const int sl = hl / G;
   const int i = hl % G;
   const int s = (int)blockIdx.x * spw + sl;
@@ -173,13 +198,13 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
   bool wrap_l = false;           // PIPE: this lane's step T - 1 takes max3 of the next-state row from the follower's log
   bool wrap_it = false;          // PIPE: the loop's last iteration of a phase (uniform)
   // PIPE: the undo log of the rows (key of step 0, temperature bin, p2p = 0) this lane's episode has
-  // stored into: max3 of each row as first read, [2 halves][32 bins][32 lanes] and a dummy slot per lane
+  // stored into: max3 of each row as first read, [KG groups][32 bins][GW lanes] and a dummy slot per lane
   // (a step that logs nothing writes there: the LDS store is unconditional); bit iT of wlog_m = logged
   QT* wlog = nullptr;
-  uint32_t* wlog_mask = nullptr;  // [64 lanes] every lane's wlog_m, for the other half's step T - 1
+  uint32_t* wlog_mask = nullptr;  // [64 lanes] every lane's wlog_m, for the other groups' step T - 1
   uint32_t wlog_m = 0u, key0 = 0u;
   if constexpr (PIPE) {
-    __shared__ QT wlog_lds[2 * 32 * 32 + kWave];
+    __shared__ QT wlog_lds[KG * 32 * GW + kWave];
     __shared__ uint32_t wlog_mask_lds[kWave];
     wlog = wlog_lds;
     wlog_mask = wlog_mask_lds;
@@ -269,11 +294,11 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
       key0 = pS[0].y & 0xFFFFu;
       wlog_m = 0u;
       wlog_mask[lane] = 0u;
-      // the T0 this half's NEXT episode (ep + 2) starts from, or the one the chain leaves behind: drawn
+      // the T0 this group's NEXT episode (ep + KG) starts from, or the one the chain leaves behind: drawn
       // while the first rows are in flight
 #if P2PMG_ABLATE != 13  // 13 (timing-only): no draw at the phase boundary (what moving it off the wave could save)
       if (active)
-        t0_draw(p.seed_lo, p.seed_hi, p.episode + (ep + 2 < n_chain ? ep + 2 : n_chain), p.agent_offset + (uint32_t)a,
+        t0_draw(p.seed_lo, p.seed_hi, p.episode + (ep + KG < n_chain ? ep + KG : n_chain), p.agent_offset + (uint32_t)a,
                 k.setpoint, p.reset_sigma, t0_in, t0_m);
 #endif
     }
@@ -434,6 +459,7 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
       code = (int)((cw >> (8 * r)) & 0xFF);
       if (CAND && r == 1) {
         // the partner's round-0 action picks the prefetched row (its bin is byte b of ipc0)
+        // (a DPP quad_perm inside the scenario's G = 2 lanes: a lane group of 32 or 16 lanes never splits a pair)
         const int b = __float_as_int(shfl_xor_c<1>(__int_as_float(act)));
 #if P2PMG_TRACE
         {
@@ -562,7 +588,7 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
 #if P2PMG_ABLATE == 11
     g = row[0];
 #else
-    exchange<N>(row, col, i, sl, nullptr);
+    exchange<N>(row, col, i, sl, nullptr);  // inside the scenario's G lanes, whatever the lane group's width
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       // ex = sign(pij) * min(|pij|, |pji|) where the signs differ (community.py:48-50)
@@ -592,11 +618,30 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
         // written by the follower since its own step 0, every such store issued before the row's load;
         // where the follower logged the row, the log holds what the serial chain reads here
         if (wrap_it) {
-          const QT sv = wlog[((grp ^ 1) * 32 + iT) * 32 + hl];
-          const uint32_t fm = wlog_mask[lane ^ 32];
+          if constexpr (KG == 2) {
+            const QT sv = wlog[((grp ^ 1) * 32 + iT) * 32 + hl];
+            const uint32_t fm = wlog_mask[lane ^ 32];
 #if P2PMG_ABLATE != 12  // 12 (test-only): the loaded row, which the follower has overwritten; the dense-collision test must then fail
-          qmax = wrap_l && ((fm >> iT) & 1u) != 0u ? sv : qmax;
+            qmax = wrap_l && ((fm >> iT) & 1u) != 0u ? sv : qmax;
 #endif
+          } else {
+            // three followers (episodes e + 1, e + 2, e + 3 in groups grp + 1, + 2, + 3 mod 4) may have stored
+            // into the row: the EARLIEST one that logged the bin read it as the serial chain leaves it for
+            // this step (a later follower's first read has seen the earlier follower's stores).  A group
+            // without a successor episode (the chain's end, the drain) reset its mask in its prologue and
+            // never logs, so it reads as "not logged".  Selected from the last follower down to the first.
+            QT pick = qmax;
+#pragma unroll
+            for (int j = KG - 1; j >= 1; --j) {
+              const int gj = (grp + j) % KG;
+              const QT sv = wlog[(gj * 32 + iT) * GW + hl];
+              const uint32_t fm = wlog_mask[gj * GW + hl];
+              pick = ((fm >> iT) & 1u) != 0u ? sv : pick;
+            }
+#if P2PMG_ABLATE != 12
+            qmax = wrap_l ? pick : qmax;
+#endif
+          }
         }
       }
       if constexpr (PIPE) {
@@ -604,7 +649,7 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
         // row as this step read it (rowR holds the lane's own previous store).  The hazard rule keeps
         // such steps out of an episode's second half.
         const bool first = st_on && (p0.y & 0xFFFFu) == key0 && ip == ip_zero && ((wlog_m >> iT) & 1u) == 0u;
-        wlog[first ? (grp * 32 + iT) * 32 + hl : 2 * 32 * 32 + lane] = max3(rowR);
+        wlog[first ? (grp * 32 + iT) * GW + hl : KG * 32 * GW + lane] = max3(rowR);
         wlog_m |= first ? 1u << iT : 0u;
         wlog_mask[lane] = wlog_m;
       }
@@ -684,33 +729,34 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
       if constexpr (BAT != 0) p.soc[a] = soc;
     }
   } else {
-    // Phase ph (L = T / 2 lockstep steps; the launcher sends T % 6 == 0, so the ring's rotation holds
-    // across phases): episode ph runs its first half in half ph & 1 of the wave, episode ph - 1 its
-    // second half in the other.  A half without an episode (the upper one in phase 0, one of them in
-    // the last phase) runs masked to the dummy slots, as inactive lanes do.
-    const int L = T / 2;
-    int ep_l = grp == 0 ? 0 : -1;  // the episode this lane's half runs
+    // Phase ph (L = T / KG lockstep steps; the launcher sends T % (3 KG) == 0, so the ring's rotation holds
+    // across phases): episode ph runs its first L steps in group ph % KG of the wave, episodes ph - 1 ..
+    // ph - KG + 1 their later phases in the other groups.  A group without an episode (fill: the groups
+    // above 0 until their first phase; drain: the groups whose next episode would be past the chain) runs
+    // masked to the dummy slots, as inactive lanes do.
+    const int L = T / KG;
+    int ep_l = grp == 0 ? 0 : grp - KG;  // the episode this lane's group runs (< 0: none yet; its prologue draws episode grp's T0)
     st_on = active && grp == 0;
-    begin_episode(ep_l);  // the upper half: only its ring, rows and episode 1's T0 draw
+    begin_episode(ep_l);  // the other groups: only their ring, rows and their first episode's T0 draw
     __builtin_amdgcn_s_waitcnt(0);
     for (int ph = 0;; ++ph) {
       if (ph > 0) {
-        if (grp == (ph & 1)) {  // this half is at an episode boundary
+        if (grp == (int)((unsigned)ph % KG)) {  // this group is at an episode boundary
           if (st_on && i == 0) {
             if (p.chain_rewards) p.chain_rewards[(size_t)ep_l * p.S + s] = ep_sum;
             if (ep_l == n_chain - 1) p.ep_reward[s] = ep_sum;
           }
-          if (ph <= n_chain) {
+          if (ph <= n_chain + KG - 2) {
             ep_l = ph;
             st_on = active && ph < n_chain;
             begin_episode(ph < n_chain ? ph : n_chain - 1);
           }
         }
-        // both halves enter the loop with nothing in flight (the other half's rows sit through this)
+        // every group enters the loop with nothing in flight (the other groups' rows sit through this)
         __builtin_amdgcn_s_waitcnt(0);
-        if (ph > n_chain) break;
+        if (ph > n_chain + KG - 2) break;
       }
-      wrap_l = st_on && grp != (ph & 1) && ep_l + 1 < n_chain;
+      wrap_l = st_on && grp == (int)((unsigned)(ph + 1) % KG) && ep_l + 1 < n_chain;  // the group in its episode's last phase
       for (int t = 0; t < L; t += 3) {
         wrap_it = t + 3 >= L;
         step(S0{});
@@ -719,14 +765,14 @@ __global__ __launch_bounds__(kWave) void episode_fast_kernel(const EpisodeParams
       }
     }
     // the T0 the chain leaves behind: drawn in the last episode's prologue
-    if (active && grp == ((n_chain - 1) & 1)) {
+    if (active && grp == (int)((unsigned)(n_chain - 1) % KG)) {
       p.t_in[a] = t0_in;
       p.t_m[a] = t0_m;
     }
   }
 }
 
-// the community sizes the two-episodes-per-wave form is instantiated for (the plan asks the same)
+// the community sizes the several-episodes-per-wave forms (KG = 2, 4) are instantiated for (the plan asks the same)
 template <int N>
 constexpr bool kFastPipe = N == 2;
 
@@ -736,8 +782,11 @@ template <int N, typename QT, int R1, int BAT, bool NARROW>
 void launch_fast_nw(const EpisodeParams& p, const uint2* pre, FastRec* recs, int blocks, int spw, int prod,
                     const PrepOut& nxt, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
   if constexpr (kFastPipe<N> && BAT == 0) {
+    if (p.mode == 0 && p.interleave == 4)
+      return hipExtLaunchKernelGGL((episode_fast_kernel<N, QT, R1, true, BAT, NARROW, 4>), dim3(blocks + prod),
+                                   dim3(kWave), 0, st, ev0, ev1, 0, p, pre, recs, spw, blocks, nxt);
     if (p.mode == 0 && p.interleave)
-      return hipExtLaunchKernelGGL((episode_fast_kernel<N, QT, R1, true, BAT, NARROW, true>), dim3(blocks + prod),
+      return hipExtLaunchKernelGGL((episode_fast_kernel<N, QT, R1, true, BAT, NARROW, 2>), dim3(blocks + prod),
                                    dim3(kWave), 0, st, ev0, ev1, 0, p, pre, recs, spw, blocks, nxt);
   }
   if (p.mode == 0)
@@ -767,9 +816,11 @@ template <int N, typename QT>
 hipError_t launch_fast_n(const EpisodeParams& p, const uint2* pre, void* recs, int spw, const PrepOut* nxt,
                          hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
   constexpr int G = pow2ceil(N);
-  // two episodes per wave need what the plan's interleave promises; anything else is a caller's error
-  if (p.interleave && !(kFastPipe<N> && p.mode == 0 && !p.battery && p.chain >= 2 && p.reset_t0 && p.T % 6 == 0 &&
-                        p.nT <= 32 && spw > 0 && spw <= kWave / 2 / G))
+  // several episodes per wave (p.interleave = 2 or 4 lane groups) need what the plan promises; anything
+  // else is a caller's error
+  const int kg = p.interleave;
+  if (kg && !((kg == 2 || kg == 4) && kFastPipe<N> && p.mode == 0 && !p.battery && p.chain >= kg && p.reset_t0 &&
+              p.T % (3 * kg) == 0 && p.nT <= 32 && spw > 0 && spw <= kWave / kg / G))
     return hipErrorInvalidValue;
   if (spw <= 0 || spw > kWave / G) spw = kWave / G;
   const int blocks = (p.S + spw - 1) / spw;

@@ -90,7 +90,7 @@ struct EpisodeParams {
   // chain_rewards[k * S + s] (when non-null).  0 or 1: one episode.
   int chain;
   // chained launch: episodes e and e + 1 of an agent run in the two halves of a wave, T / 2 steps
-  // apart (the plan's interleave; the kernel's PIPE form)
+  // apart (the plan's interleave; the kernel's PIPE form): the lane groups per wave, 0 (serial), 2 or 4
   int interleave;
   size_t codes_stride;
   float* chain_rewards;

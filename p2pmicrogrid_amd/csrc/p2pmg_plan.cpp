@@ -71,6 +71,11 @@ EpisodePlan plan_episode(const PlanFacts& c, const p2pmg_episode_args& args, boo
   // table rows apart (chain_lag_ok)
   pl.interleave = fast && chained && n_chain >= 2 && philox && (args.flags & P2PMG_FLAG_RESET_T0) != 0 && !c.battery &&
                   c.T % 6 == 0 && g.n_temp_states <= 32 && c.N == 2 && c.chain_lag_ok && !ov.no_interleave;
+  // four, a quarter episode apart, where the phases keep the input ring's rotation (T % 12 == 0), the
+  // hazard distance fits a quarter (chain_lag_ok4) and the chain fills every group; else two under the
+  // rule above, else the serial chain
+  const bool quad = pl.interleave && c.T % 12 == 0 && c.chain_lag_ok4 && n_chain >= 4 && ov.max_groups >= 4;
+  pl.groups = quad ? 4 : pl.interleave ? 2 : 1;
   int spw = args.scen_per_wave > 0 ? args.scen_per_wave : ov.spw;
   if (spw <= 0) {  // automatic: full waves, or spread a small batch over all CUs (one wave per CU)
     const int full = 64 / (c.N <= 1 ? 1 : c.N <= 2 ? 2 : c.N <= 4 ? 4 : 8);
@@ -83,7 +88,7 @@ EpisodePlan plan_episode(const PlanFacts& c, const p2pmg_episode_args& args, boo
     if (fast && train && args.epsilon < 0.5 && waves < c.n_cu) spw = std::max(full / 4, (spw + 1) / 2);
     spw = std::min(spw, full);
   }
-  if (pl.interleave) spw = std::min(spw, 32 / 2);  // a scenario's lanes stay inside one half of the wave
+  if (pl.interleave) spw = std::min(spw, 64 / pl.groups / 2);  // a scenario's lanes stay inside one lane group (N = 2)
   pl.spw = spw;
   return pl;
 }

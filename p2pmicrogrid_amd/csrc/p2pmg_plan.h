@@ -24,6 +24,8 @@ struct PlanFacts {
   // the uploaded inputs' hazard distance D allows two chained episodes per wave, half an episode apart:
   // D + 4 <= T / 2 (chain_lag_kernel in p2pmg_small.hip, once per upload)
   bool chain_lag_ok = false;
+  // ... and four, a quarter episode apart: D + 4 <= T / 4 (adjacent episodes decide)
+  bool chain_lag_ok4 = false;
 };
 
 // the environment overrides (the runtime reads them once per process)
@@ -32,6 +34,7 @@ struct Overrides {
   int spw = 0;           // P2PMG_SPW: scenarios per wave where the arguments leave it automatic
   bool no_spec = false;  // P2PMG_NO_SPEC=1 (profiling only): no producer blocks, so the episode kernel's counters are its own
   bool no_interleave = false;  // P2PMG_INTERLEAVE=0 (A/B runs): chained launches run their episodes one after the other
+  int max_groups = 4;          // P2PMG_INTERLEAVE=2 (A/B runs, tests): at most two chained episodes per wave
 };
 
 enum class Family { General, Tile, Fast, Sq16 };  // Tile: the general kernel's LDS-tile form
@@ -45,7 +48,8 @@ struct EpisodePlan {
   int rec_narrow = 0;           // fast / sq16: only {reward, cost} requested -> 8-B record rows
   bool packed_records = false;  // the launch writes packed rows (rec_pack) and stamps its own timing events
   bool speculate = false;       // fast: extra workgroups compute the next launch's pre-pass
-  bool interleave = false;      // fast, chained: episodes e and e + 1 of an agent in the two halves of a wave, T / 2 steps apart
+  bool interleave = false;      // fast, chained: consecutive episodes of an agent in the lane groups of a wave, T / groups steps apart
+  int groups = 1;               // ... how many: 1 (serial), 2 (halves of the wave) or 4 (quarters)
   const char* error = nullptr;  // the request is refused (P2PMG_E_INVALID) with this message
 };
 

@@ -322,7 +322,9 @@ const p2pmg::Overrides& overrides() {
   static const p2pmg::Overrides ov = [] {
     const char *k = getenv("P2PMG_KERNEL"), *w = getenv("P2PMG_SPW"), *n = getenv("P2PMG_NO_SPEC");
     const char* il = getenv("P2PMG_INTERLEAVE");
-    return p2pmg::Overrides{k && !strcmp(k, "general"), w ? atoi(w) : 0, n && atoi(n) != 0, il && atoi(il) == 0};
+    // P2PMG_INTERLEAVE: 0 = serial chains, 2 = at most two episodes per wave, anything else = the plan's choice
+    return p2pmg::Overrides{k && !strcmp(k, "general"), w ? atoi(w) : 0, n && atoi(n) != 0, il && atoi(il) == 0,
+                            il && atoi(il) == 2 ? 2 : 4};
   }();
   return ov;
 }
@@ -1167,6 +1169,7 @@ static int update_chain_lag(p2pmg_ctx* c, const uint2* pre) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   c->chain_lag_ok = c->chain_lag >= 0 && c->chain_lag + 4 <= c->T / 2;
+  c->chain_lag_ok4 = c->chain_lag >= 0 && c->chain_lag + 4 <= c->T / 4;
   c->lag_version = c->inputs_version;
   return P2PMG_OK;
 }
@@ -1196,7 +1199,7 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
     RC_TRY(update_chain_lag(c, c->pre[ps]));
     plan = p2pmg::plan_episode(*c, *args, true, overrides(), ch->n);  // ... with the fact it was missing
   }
-  p.interleave = plan.interleave ? 1 : 0;
+  p.interleave = plan.interleave ? plan.groups : 0;
   p.rec_narrow = plan.rec_narrow;
   const bool reset = (args->flags & P2PMG_FLAG_RESET_T0) != 0;
   p.reset_t0 = (ext && reset) ? 1 : 0;
@@ -1223,7 +1226,7 @@ static int run_episode_impl(p2pmg_ctx* c, const p2pmg_episode_args* args, const 
                     // sq16 draws in the kernel by default: a launch that read pre-pass code words instead says so
                     (sq16 && plan.philox == p2pmg::Philox::CodesPrepass ? ",philox-prepass" : "") +
                     (c->battery ? (ext && !p.bat_safe ? ",battery,range-checked>" : ",battery>")
-                                : plan.interleave ? ",interleaved>" : ">"),
+                                : plan.interleave ? ",K=" + std::to_string(plan.groups) + ",interleaved>" : ">"),
                 args->record, ext ? (args->record & 127) : 0, plan.rec_narrow);
   return P2PMG_OK;
 }
