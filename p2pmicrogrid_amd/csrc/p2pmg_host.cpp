@@ -1,0 +1,114 @@
+// p2pmg_host.cpp — the entry points that touch neither HIP nor a context, and the config check
+// p2pmg_create makes before its first device call.  No HIP include: tests/host_check.cpp links this file
+// alone into a program that runs under sanitizers.
+#include "p2pmg_host.h"
+
+#include <cstdint>
+#include <cstring>
+
+namespace p2pmg {
+
+int validate_config(const p2pmg_config* cfg, std::string* why) {
+  if (why) why->clear();
+  if (!cfg) return P2PMG_E_INVALID;
+  if (cfg->n_scenarios <= 0 || cfg->n_agents <= 0 || cfg->rounds < 0 || cfg->horizon <= 0) return P2PMG_E_INVALID;
+  if (cfg->rounds + 1 > kMaxRounds1) return P2PMG_E_UNSUPPORTED;
+  // 2 actions: a context that holds tables (set_q, get_q, the table digests) but runs no episode
+  if (cfg->n_actions != 3 && !(cfg->n_actions == 2 && cfg->learner == P2PMG_LEARNER_TABULAR)) return P2PMG_E_UNSUPPORTED;
+  // any community size a scenario's wave holds (get_community takes any n_agents, community.py:198-204)
+  if (cfg->n_agents > kMaxAgents) return P2PMG_E_UNSUPPORTED;
+  if (cfg->q_dtype != P2PMG_Q_F64 && cfg->q_dtype != P2PMG_Q_F32) return P2PMG_E_INVALID;
+  if (cfg->shared_q == P2PMG_SHARED_ROLE && cfg->learner == P2PMG_LEARNER_DQN) {
+    if (why) *why = "create: shared_q = P2PMG_SHARED_ROLE needs learner = TABULAR (a Q-network per role is not built)";
+    return P2PMG_E_UNSUPPORTED;
+  }
+  return P2PMG_OK;
+}
+
+}  // namespace p2pmg
+
+extern "C" {
+
+int p2pmg_abi_version(void) { return P2PMG_ABI_VERSION; }
+
+int p2pmg_config_default(p2pmg_config* cfg) {
+  if (!cfg) return P2PMG_E_INVALID;
+  std::memset(cfg, 0, sizeof(*cfg));
+  cfg->n_scenarios = 1;
+  cfg->n_agents = 2;   // setup.py:33
+  cfg->rounds = 1;     // setup.py:34
+  cfg->horizon = 96;   // one day of 15-minute slots
+  cfg->q_dtype = P2PMG_Q_F64;
+  cfg->n_time_states = cfg->n_temp_states = cfg->n_balance_states = cfg->n_p2p_states = 20;
+  cfg->n_actions = 3;
+  cfg->alpha = 1e-5;
+  cfg->gamma = 0.9;
+  const double levels[3] = {0.0, 0.5, 1.0};
+  for (int k = 0; k < 3; ++k) cfg->hp_levels[k] = (float)(levels[k] * 3e3);
+  cfg->setpoint = 21.0f;
+  cfg->temp_margin = 1.0f;
+  cfg->lower_bound = 20.0f;
+  cfg->upper_bound = 22.0f;
+  const double Ci = 2.44e6 * 2, Cm = 9.4e7, Ri = 8.64e-4, Re = 1.05e-2, Rvent = 7.98e-3, gA = 11.468, f_rad = 0.3;
+  cfg->inv_ci = (float)(1 / Ci);
+  cfg->inv_cm = (float)(1 / Cm);
+  cfg->inv_ri = (float)(1 / Ri);
+  cfg->inv_re = (float)(1 / Re);
+  cfg->inv_rvent = (float)(1 / Rvent);
+  cfg->one_minus_frad = (float)(1 - f_rad);
+  cfg->frad = (float)f_rad;
+  cfg->solar_gain = (float)(gA * 0.0);
+  cfg->hp_cop = 3.0f;
+  cfg->seconds_per_minute = 60.0f;
+  cfg->time_slot = 15.0f;
+  cfg->minutes_per_hour = 60.0f;
+  cfg->kilo = (float)1e-3;
+  cfg->penalty_weight = 10.0f;
+  cfg->seed = 42;
+  cfg->scenario_offset = 0;
+  return P2PMG_OK;
+}
+
+int p2pmg_dqn_config_default(p2pmg_dqn_config* cfg) {
+  if (!cfg) return P2PMG_E_INVALID;
+  std::memset(cfg, 0, sizeof(*cfg));
+  cfg->gamma = 0.95;  // agent.py:309
+  cfg->tau = 0.005;
+  cfg->lr = 1e-5;     // agent.py:310
+  cfg->beta1 = 0.9;
+  cfg->beta2 = 0.999;
+  cfg->adam_eps = 1e-7;
+  cfg->clip = 1.0;    // rl.py:329
+  cfg->batch = 32;    // agent.py:308
+  cfg->capacity = 5000;
+  cfg->agents_per_block = 0;
+  return P2PMG_OK;
+}
+
+int p2pmg_replay_decode(const uint32_t* words, size_t n_words, size_t n_decisions, const double* eps, size_t n_eps,
+                        uint8_t* codes, size_t* consumed) {
+  if (!words || !eps || n_eps == 0 || !codes) return P2PMG_E_INVALID;
+  size_t pos = 0;
+  for (size_t k = 0; k < n_decisions; ++k) {
+    // RandomState.rand(): (a * 2^26 + b) / 2^53 with a = w0 >> 5, b = w1 >> 6 (mt19937 next_double)
+    if (pos + 2 > n_words) return P2PMG_E_INVALID;
+    const uint32_t a = words[pos] >> 5, b = words[pos + 1] >> 6;
+    pos += 2;
+    const double u = ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
+    if (u < eps[k % n_eps]) {
+      // RandomState.choice(3) -> randint(0, 3): masked rejection, mask 3, one word per try
+      uint32_t v;
+      do {
+        if (pos >= n_words) return P2PMG_E_INVALID;
+        v = words[pos++] & 3u;
+      } while (v > 2u);
+      codes[k] = (uint8_t)v;
+    } else {
+      codes[k] = P2PMG_GREEDY;
+    }
+  }
+  if (consumed) *consumed = pos;
+  return P2PMG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,20 @@
+// p2pmg_host.h — what the runtime decides without HIP and without a context (p2pmg_host.cpp): the bounds
+// of a config and their check.  Includes no HIP header, so a program without a GPU can check it
+// (tests/test_cpu_host_unit.py).
+#pragma once
+#include <string>
+
+#include "p2pmg.h"
+
+namespace p2pmg {
+
+constexpr int kMaxAgents = 64;  // agents per scenario: one 64-lane wave holds a scenario (general kernel)
+// R + 1 rounds: no kernel limit (rounds 8 and above read their codes per round); the bound only keeps
+// the per-step code and record arrays ([T][ceil((R+1)/4)][A], [T][R+1][A]) in 32-bit row counts
+constexpr int kMaxRounds1 = 4096;
+
+// What p2pmg_create checks before it allocates a context: P2PMG_OK, or the status create returns, with
+// *why (cleared first) the message p2pmg_last_error(NULL) then gives, where there is one.  Not exported.
+__attribute__((visibility("hidden"))) int validate_config(const p2pmg_config* cfg, std::string* why);
+
+}  // namespace p2pmg

@@ -1,19 +1,18 @@
 // Internal declarations shared by the kernel units (device code + launchers: p2pmg_general.hip,
 // p2pmg_fast.hip, p2pmg_sq16.hip, p2pmg_small.hip, p2pmg_dqn.hip, p2pmg_dqn_map.hip, p2pmg_summary.hip, p2pmg_tables.hip) and
-// p2pmg_runtime.cpp (context, C ABI).  Not part of the public ABI (include/p2pmg.h).
+// the runtime units (p2pmg_rt_*.cpp: context, C ABI; their own shared header is p2pmg_ctx.h).  Not part of
+// the public ABI (include/p2pmg.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "p2pmg_host.h"  // kMaxAgents, kMaxRounds1
 
 namespace p2pmg {
 
 constexpr int kEnvStride = 8;  // floats per env row: time, t_out, buy, inj, p2p, pad x3
 constexpr int kQPad = 4;       // Q row padded to 4 actions: 32-B (f64) / 16-B (f32) aligned rows
 constexpr int kWave = 64;      // one wave per workgroup
-constexpr int kMaxAgents = 64;  // agents per scenario: one 64-lane wave holds a scenario (general kernel)
-// R + 1 rounds: no kernel limit (rounds 8 and above read their codes per round); the bound only keeps
-// the per-step code and record arrays ([T][ceil((R+1)/4)][A], [T][R+1][A]) in 32-bit row counts
-constexpr int kMaxRounds1 = 4096;
 // capacity of the general kernel's LDS-tile form for n agents (16, 32 or 64)
 inline constexpr int general_tile_cap(int n) { return n <= 16 ? 16 : (n <= 32 ? 32 : 64); }
 constexpr double kDeltaScale = 1099511627776.0;  // 2^40: shared-table TD deltas in int64 fixed point

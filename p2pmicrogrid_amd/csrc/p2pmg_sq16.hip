@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kWave * kSq16Waves, P2PMG_SQ16_OCC) void episode_sq
   const size_t A = (size_t)p.A;
   const KC k = scalar_constants(p);
   const Dims<true> D{k.nt, k.nT, k.nb, k.np};
-  // the launcher sends this kernel 20^4 tables only (p2pmg_runtime.cpp, sq16 dispatch): the state
+  // the launcher sends this kernel 20^4 tables only (p2pmg_plan.cpp, the Sq16 family): the state
   // count is a literal, not four kernel arguments kept in SGPRs across the loop
   constexpr uint32_t n_states = 20u * 20u * 20u * 20u;
   const QT* __restrict__ q = reinterpret_cast<const QT*>(p.q);
