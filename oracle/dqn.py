@@ -136,7 +136,7 @@ def gradients(theta, s, a, r, ns, target, gamma: float, clip: float = 1.0):
 
 
 # ----------------------------------------------------------------------------- device order
-# The same arithmetic in the summation order of the HIP kernels (p2pmg_dqn.hip), so the device
+# The same arithmetic in the summation order of the HIP kernels (p2pmg_dqn_*.hip), so the device
 # can be held to it bit for bit.  The f32 MFMA is exactly a k-ordered fmaf chain (MI355X guide,
 # FP32-input MFMA numerics), DPP / permlane sums are the pairwise trees spelled out below, and
 # every other op rounds on its own (-ffp-contract=off).  forward()/gradients() above (NumPy

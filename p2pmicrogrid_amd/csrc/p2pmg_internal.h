@@ -1,5 +1,5 @@
 // Internal declarations shared by the kernel units (device code + launchers: p2pmg_general.hip,
-// p2pmg_fast.hip, p2pmg_sq16.hip, p2pmg_small.hip, p2pmg_dqn.hip, p2pmg_dqn_map.hip, p2pmg_summary.hip, p2pmg_tables.hip) and
+// p2pmg_fast.hip, p2pmg_sq16.hip, p2pmg_small.hip, p2pmg_dqn_*.hip, p2pmg_summary.hip, p2pmg_tables.hip) and
 // the runtime units (p2pmg_rt_*.cpp: context, C ABI; their own shared header is p2pmg_ctx.h).  Not part of
 // the public ABI (include/p2pmg.h).
 #pragma once
@@ -148,6 +148,9 @@ struct DqnParams {
   int fold_spt;              // segment fold: runs per thread (0 auto: 4 for runs <= 8, else 1 = the reduce kernel)
 };
 hipError_t launch_dqn_act(const DqnParams& p, hipStream_t stream);
+// launch_dqn_act's branch for one shared network on MFMA tiles, taken when act_shared_mfma(p)
+bool act_shared_mfma(const DqnParams& p);
+hipError_t launch_dqn_act_shared(const DqnParams& p, hipStream_t stream);
 hipError_t launch_dqn_sample(const DqnParams& p, hipStream_t stream);
 // every env step's Philox replay draws of the episode p describes, as deque indices [T][A][32] u16
 // (the replay-mode sample layout), from the episode-start counts d.added

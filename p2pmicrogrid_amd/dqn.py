@@ -6,7 +6,7 @@ network, the data-parallel config 5) an online and a target ``QNetwork`` (rl.py:
 One ``run_episode`` call runs T environment steps on the device; each step is an act launch
 (negotiation rounds with the Q-MLP, market, reward, memory append, RC update) followed in
 TRAIN mode by the train launch (sample 32, target/online forward + backward on f32 MFMA,
-clip, Adam, soft update; p2pmg_dqn.hip).
+clip, Adam, soft update; p2pmg_dqn_*.hip).
 
     mode 'fill'   CommunityMicrogrid.init_buffers (community.py:125-147): act + remember
     mode 'train'  CommunityMicrogrid.train_episode (community.py:149-182) with DQNAgent.train

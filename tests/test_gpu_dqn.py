@@ -196,8 +196,10 @@ def _compare_episode(eng, out, mode, eps):
                                                        (2, 10, 1, False, 0, 1), (1, 20, 2, True, 4, 1),
                                                        (1, 33, 0, False, 0, 1), (2, 3, 8, True, 2, 1),
                                                        # 8 segments (the act kernel's fused Adam step at
-                                                       # its limit) and 16 (the standalone Adam launch)
-                                                       (8, 2, 1, True, 2, 8), (16, 1, 1, True, 1, 16)])
+                                                       # its limit), 16 (the standalone Adam launch) and
+                                                       # 17 (its loop past one 16-segment batch)
+                                                       (8, 2, 1, True, 2, 8), (16, 1, 1, True, 1, 16),
+                                                       (17, 1, 1, True, 1, 17)])
 def test_episodes_match_oracle(S, N, R, shared, apb, segments):
     """Fill + two training episodes + a greedy day, bit for bit: records, replay rings, losses,
     weights, target and Adam state (shared network: blocks of apb agents, `segments` gradient
