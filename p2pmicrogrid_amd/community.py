@@ -18,6 +18,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import database as db
+from . import day_profile as dayprof
 from . import dataset as ds
 from . import setup
 from .agent import ActingAgent, Agent, DQNAgent, GridAgent, QAgent, RuleAgent, agent_kind
@@ -46,6 +47,11 @@ def thermal_arrays(agents) -> Tuple[np.ndarray, np.ndarray]:
     return levels, params
 
 
+def _drop_groups(profile):
+    """A one-group day profile without its G axis: {"agent": {name: [P, N]}, "community": {name: [P]}}."""
+    return {part: {k: v[0] for k, v in d.items()} for part, d in profile.items()}
+
+
 def learning_arrays(agents) -> Tuple[np.ndarray, np.ndarray]:
     """Each agent's own QActor learning rate and discount (rl.py:58-71): (alpha [N], gamma [N]) f64,
     what DeviceCommunityBatch.set_learning takes.  Pure NumPy."""
@@ -72,6 +78,7 @@ class CommunityMicrogrid:
         self._q_dtype = q_dtype or setup.q_dtype
         self._device = setup.device if device is None else device
         self._engine: Optional[DeviceCommunityBatch] = None
+        self._last_run = None  # what day_profile() reduces: the last run()'s records and the inputs it ran with
         self._uploaded: Dict[str, Any] = {}
         self._rng = ReferenceRNG()
         kinds = {agent_kind(a) for a in agents}
@@ -141,6 +148,7 @@ class CommunityMicrogrid:
             eng.set_profiles(load, pv)
             eng.set_max_in(np.array([F32(a.max_in) for a in self.agents], F32)[None])
             self._uploaded["prof"] = prof_key
+            self._prof_host = (np.asarray(load, F32), np.asarray(pv, F32))
         # every agent's own heat-pump levels, setpoint, comfort band and COP: keyed on the values, so
         # a change between calls (e.g. agent.heating.hp.max_power = ...) is uploaded again
         levels, params = thermal_arrays(self.agents)
@@ -248,6 +256,7 @@ class CommunityMicrogrid:
         eng.run_episode("greedy", record=rec)
         self._pull_storage(eng, T)
         r = eng.get_records(rec)
+        self._keep_run(r)
         self._pull_records(eng, T)
         t_in, t_m = eng.get_temperatures()
         hist = r["t_in"][:, 0, :]
@@ -265,6 +274,20 @@ class CommunityMicrogrid:
         if self._engine is None:
             raise RuntimeError("summary() describes the last run(): call run() first")
         return {k: v[0] for k, v in self._engine.episode_summary(kwh=kwh)["agent"].items()}
+
+    def _keep_run(self, records) -> None:
+        levels, params = thermal_arrays(self.agents)
+        self._last_run = (records, levels[None], *self._prof_host, params[None, :, 1], params[None, :, 2])
+
+    def day_profile(self, period: Optional[int] = None, kwh: bool = False) -> Dict[str, Dict[str, np.ndarray]]:
+        """After run(): the run by time slot, {"agent": {name: [P, N] f64}, "community": {name: [P] f64}} with
+        slot(t) = t % period (None: one slot per step; e.g. 96 folds a run of several days onto one): means,
+        action and discomfort shares, net flows and extrema per slot (day_profile.as_dict), from the records
+        run() has already brought to the host (day_profile.from_records).  kwh: mean powers as kWh per step."""
+        if self._last_run is None:
+            raise RuntimeError("day_profile() describes the last run(): call run() first")
+        scale = float(setup.TIME_SLOT) / 60.0 * 1e-3 if kwh else 1.0
+        return _drop_groups(dayprof.as_dict(*dayprof.from_records(*self._last_run, period=period), energy_scale=scale))
 
     def table_stats(self) -> Dict[str, np.ndarray]:
         """Per agent: how much of its Q-table is written, its value range and its greedy-action histogram,
@@ -293,7 +316,7 @@ class CommunityMicrogrid:
             return np.stack([p[0] for p in per]), np.stack([p[1] for p in per])
         return np.stack(per)
 
-    def run_days(self, days, summary: bool = False) -> List[Dict[str, np.ndarray]]:
+    def run_days(self, days, summary: bool = False, profile: bool = False, period: Optional[int] = None):
         """run() of this community over several days in ONE greedy launch: a per-role-table engine
         (``shared_q="role"``) with one scenario per day, holding one copy of every agent's table
         instead of one per day.  ``days``: a sequence of dicts {"time" [T], "t_out" [T], "load" [N, T],
@@ -303,6 +326,9 @@ class CommunityMicrogrid:
         from that day's inputs.  The agents' tables are read, nothing else of the community changes.
         ``summary=True`` adds "summary": {name: [N] f64} per day, the day's totals per agent
         (engine.SUMMARY_FIELDS) from one device-side reduction of the launch's records.
+        ``profile=True`` returns (that list, the mean day): {"agent": {name: [P, N] f64}, "community":
+        {name: [P] f64}}, the days reduced per time slot and agent (day_profile.from_records on the records this
+        call returns anyway, the days being the launch's scenarios; ``period``: slots, None = T).
         Tabular communities only."""
         if self._rule or self._dqn:
             raise NotImplementedError("run_days needs tabular (QAgent) agents: per-role tables hold Q-tables, "
@@ -311,7 +337,7 @@ class CommunityMicrogrid:
             raise NotImplementedError("run_days does not carry battery state across days")
         D, N = len(days), len(self.agents)
         if D == 0:
-            return []
+            return ([], None) if profile else []
         T = len(np.asarray(days[0]["time"]).reshape(-1))
 
         def stack(key, shape):
@@ -321,7 +347,8 @@ class CommunityMicrogrid:
         try:
             eng.set_q(np.stack([a.actor.q_table for a in self.agents]))
             eng.set_env(time_f, t_out, *price_table(time_f))
-            eng.set_profiles(stack("load", (N, T)), stack("pv", (N, T)))
+            load, pv = stack("load", (N, T)), stack("pv", (N, T))
+            eng.set_profiles(load, pv)
             eng.set_max_in(np.broadcast_to(np.array([F32(a.max_in) for a in self.agents], F32), (D, N)))
             levels, params = thermal_arrays(self.agents)
             eng.set_hp_levels(np.broadcast_to(levels, (D, N, 3)))
@@ -345,6 +372,9 @@ class CommunityMicrogrid:
                         "t_in": r["t_in"][:, d, :], "t_in_final": t_in[d], "t_m_final": t_m[d]})
             if totals is not None:
                 out[-1]["summary"] = {k: v[d] for k, v in totals.items()}
+        if profile:
+            arrays = dayprof.from_records(r, np.broadcast_to(levels, (D, N, 3)), load, pv, par[..., 1], par[..., 2], period=period)
+            return out, _drop_groups(dayprof.as_dict(*arrays))
         return out
 
     def _run_rule(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -358,6 +388,7 @@ class CommunityMicrogrid:
         rec = ("grid", "p2p", "cost", "t_in", "action")
         eng.run_rule_episode(record=rec)
         r = eng.get_records(rec)
+        self._keep_run(r)
         self._pull_records(eng, eng.T)
         t_in, t_m = eng.get_temperatures()
         on = eng.get_hp_state()[0]

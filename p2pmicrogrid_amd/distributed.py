@@ -116,6 +116,14 @@ def all_gather_concat(values: np.ndarray, world: int) -> np.ndarray:
     return np.concatenate(out)
 
 
+def merge_day_profiles(parts):
+    """The day profiles (day_profile.from_records' four arrays) of the shards' disjoint scenario sets merged into
+    the whole batch's: integers add, extrema take min / max, so the result equals one profile over all scenarios
+    bit for bit for any world size (day_profile.merge).  Pure NumPy on the host: no collective is involved."""
+    from . import day_profile
+    return day_profile.merge(parts)
+
+
 class ShardedTrainer:
     """Training of S_total scenarios sharded over the ranks: tabular Q-learning (the reference's
     QAgent) or, with learner="dqn", DQN agents sharing ONE Q-network (config 5).
