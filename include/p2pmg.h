@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag, p2pmg_set_learning, p2pmg_get_learning, p2pmg_run_episodes_eps, p2pmg_table_stats, p2pmg_greedy_policy, p2pmg_policy_mark, p2pmg_policy_changes, n_actions = 2 table-only contexts, p2pmg_sparse_count, p2pmg_get_q_sparse, p2pmg_set_q_sparse, p2pmg_copy_q) */
+#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag, p2pmg_set_learning, p2pmg_get_learning, p2pmg_run_episodes_eps, p2pmg_table_stats, p2pmg_greedy_policy, p2pmg_policy_mark, p2pmg_policy_changes, n_actions = 2 table-only contexts, p2pmg_sparse_count, p2pmg_get_q_sparse, p2pmg_set_q_sparse, p2pmg_copy_q, p2pmg_day_profile_shape, p2pmg_day_profile) */
 
 typedef struct p2pmg_ctx p2pmg_ctx;
 
@@ -404,6 +404,66 @@ int p2pmg_get_record(p2pmg_ctx* ctx, int which, void* host);
 #define P2PMG_SUMMARY_RECORDS (P2PMG_REC_COST | P2PMG_REC_GRID | P2PMG_REC_P2P | P2PMG_REC_TEMP | P2PMG_REC_ACTION)
 /* per_agent [A][16] f64 and/or per_scenario [S][16] f64 (either may be NULL, not both) */
 int p2pmg_episode_summary(p2pmg_ctx* ctx, double* per_agent, double* per_scenario);
+/* Day profile: the records of the LAST episode launch reduced over SCENARIOS ON THE DEVICE, where
+ * p2pmg_episode_summary reduces them over time: one row per (group g, slot p = t % P, agent position i) and
+ * one per (g, p) for the community's net grid load (the means and bands behind the reference's make_day_plot,
+ * make_baseline_day_plot, make_decisions_comparison_plot and plot_grid_load, data_analysis.py), so that only
+ * [G][P][N] rows are copied to the host instead of the per-step records.  A post-pass over what the launch
+ * wrote, with p2pmg_episode_summary's requirements: every bit of P2PMG_SUMMARY_RECORDS (else P2PMG_E_STATE,
+ * p2pmg_last_error names what is missing; the narrow reward + cost form and "no episode has run" included),
+ * P2PMG_REC_REWARD optional (without it column 2 is 0).  After p2pmg_run_episodes it describes the last
+ * episode of the chain.  load and pv are read from the context's profile buffer, hp levels and comfort
+ * bounds from the per-agent arrays, as they are at the call.  Tabular, rule and DQN contexts alike.
+ * Stream-ordered, synchronises before returning.
+ *
+ * A sample is a pair (s, t) with s in the scenario range, groups[s] = g >= 0, t in the step range and
+ * t % P = p; for each agent i (a = s N + i) it adds to row [g][p][i], with fix(x, k) = rint(f64(x) * 2^k) to
+ * nearest even as int64 (f32 * 2^k is exact in f64: one rounding) and max(x, 0) = x > 0 ? x : +0:
+ *   sums [G][P][N][16] int64
+ *      0 samples            1
+ *      1 cost               fix(cost[t,a], 28)
+ *      2 reward             fix(reward[t,a], 28)              (0 when not recorded)
+ *      3 grid_import        fix(max(grid[t,a], 0), 16)        W
+ *      4 grid_export        fix(max(-grid[t,a], 0), 16)
+ *      5 p2p_import         fix(max(p2p[t,a], 0), 16)
+ *      6 p2p_export         fix(max(-p2p[t,a], 0), 16)
+ *      7 hp                 fix(hp_levels[a][action[t,R,a]], 16): the final round's action
+ *      8 load               fix(load_w[a][t], 16)
+ *      9 pv                 fix(pv_w[a][t], 16)
+ *     10 t_in               fix(T_in[t,a], 24)                degC
+ *     11 discomfort_deg     fix(d, 24), d = max(max(0, lower_a - T_in), max(0, T_in - upper_a)) as field 10 of
+ *                           p2pmg_episode_summary
+ *     12 discomfort_steps   d > 0
+ *     13 action1            action[t,R,a] == 1
+ *     14 action2            action[t,R,a] == 2
+ *     15 importing          grid[t,a] > 0
+ *   extrema [G][P][N][8] f32: min, max of T_in, grid, p2p, cost over the row's samples, zeros as +0.0; a row
+ *      without samples holds +inf, -inf
+ *   com_sums [G][P][4] int64: samples; fix(max(G_t, 0), 16); fix(max(-G_t, 0), 16); G_t > 0, with G_t the
+ *      sequential f32 sum over i = 0..N-1 of grid[t, s N + i] from +0.0 (plot_grid_load); this order is part of
+ *      the definition
+ *   com_extrema [G][P][2] f32: min, max of G_t (zeros as +0.0; +inf, -inf without samples)
+ * Every entry is an exact integer or an extremum, so none depends on the order of the reduction, and the
+ * arrays of disjoint scenario sets merge exactly (integers add, minima and maxima combine).  Records are
+ * finite.  With magnitudes below 2^23 W, 2^15 degC and 2^11 money and at most 2^24 samples per row no sum
+ * reaches 2^63: a call whose largest group times ceil(steps / P) exceeds 2^24 is P2PMG_E_INVALID (split by
+ * scenario range and merge the parts).  A bad period, range or label is P2PMG_E_INVALID with a message.
+ * The LDS a workgroup may use for its tile of rows is P2PMG_DAYPROF_TILE_BYTES (environment, read at every
+ * call; default 32768, at most 65536); when one slot of every group does not fit, the pass adds to the
+ * output with global atomics directly. */
+typedef struct p2pmg_day_profile_args {
+  int32_t period;                  /* P slots, slot(t) = t % P; 0: T (no folding); else 1..T */
+  int32_t step_first, step_count;  /* half-open range of steps; count < 0: to T; 0 is valid (empty rows) */
+  int32_t scen_first, scen_count;  /* the same over scenarios */
+  int32_t n_groups;                /* G; 0: max label + 1, at least 1 */
+  const int32_t* groups;           /* host [S], labels in [-1, G), -1 leaves a scenario out; NULL: all 0 */
+} p2pmg_day_profile_args;
+/* G and P of a call with these arguments (either may be NULL); the arguments are checked as by the call */
+int p2pmg_day_profile_shape(p2pmg_ctx* ctx, const p2pmg_day_profile_args* args, int32_t* G, int32_t* P);
+/* any output may be NULL, not all four */
+int p2pmg_day_profile(p2pmg_ctx* ctx, const p2pmg_day_profile_args* args, int64_t* sums /* [G][P][N][16] */,
+                      float* extrema /* [G][P][N][8] */, int64_t* com_sums /* [G][P][4] */,
+                      float* com_extrema /* [G][P][2] */);
 /* fast path: episode launches whose step pre-pass the previous launch had already produced (hits)
  * and launches that had to run it themselves (misses), since the context was created */
 int p2pmg_prepass_stats(p2pmg_ctx* ctx, int64_t* hits, int64_t* misses);

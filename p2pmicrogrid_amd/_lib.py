@@ -53,6 +53,7 @@ EXPORTS = [
     "p2pmg_dqn_set_grid", "p2pmg_dqn_get_grid", "p2pmg_dqn_policy_map", "p2pmg_dqn_map_stats", "p2pmg_dqn_policy_mark",
     "p2pmg_dqn_policy_changes",
     "p2pmg_sparse_count", "p2pmg_get_q_sparse", "p2pmg_set_q_sparse", "p2pmg_copy_q",
+    "p2pmg_day_profile_shape", "p2pmg_day_profile",
 ]
 
 
@@ -87,6 +88,11 @@ class EpisodeArgs(C.Structure):
     _fields_ = [("mode", C.c_int32), ("rng", C.c_int32), ("episode", C.c_int32), ("record", C.c_int32),
                 ("epsilon", C.c_double), ("flags", C.c_int32), ("scen_per_wave", C.c_int32),
                 ("reset_sigma", C.c_double), ("next_epsilon", C.c_double)]
+
+
+class DayProfileArgs(C.Structure):
+    _fields_ = [("period", C.c_int32), ("step_first", C.c_int32), ("step_count", C.c_int32), ("scen_first", C.c_int32),
+                ("scen_count", C.c_int32), ("n_groups", C.c_int32), ("groups", C.c_void_p)]
 
 
 FLAG_PHILOX_PREPASS, FLAG_PHILOX_INKERNEL, FLAG_GENERAL_KERNEL, FLAG_RESET_T0, FLAG_NEXT_EPSILON = 1, 2, 4, 8, 16
@@ -141,6 +147,9 @@ def _declare(lib):
         "p2pmg_get_record": ([vp, i32, vp], i32),
         "p2pmg_get_episode_reward": ([vp, fp], i32),
         "p2pmg_episode_summary": ([vp, vp, vp], i32),
+        "p2pmg_day_profile_shape": ([vp, C.POINTER(DayProfileArgs), C.POINTER(C.c_int32), C.POINTER(C.c_int32)], i32),
+        # sums [G][P][N][16] i64, extrema [G][P][N][8] f32, com_sums [G][P][4] i64, com_extrema [G][P][2] f32
+        "p2pmg_day_profile": ([vp, C.POINTER(DayProfileArgs), vp, vp, vp, vp], i32),
         "p2pmg_last_kernel_ms": ([vp, C.POINTER(C.c_float)], i32),
         "p2pmg_rc_step": ([vp, i32, fp, fp, fp, fp, fp, fp], i32),
         "p2pmg_rc_step_ex": ([vp, i32, fp, fp, fp, fp, vp, C.c_float, fp, fp], i32),

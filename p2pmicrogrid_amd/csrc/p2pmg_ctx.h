@@ -151,6 +151,11 @@ struct p2pmg_ctx : p2pmg::PlanFacts {
   DevBuf<int32_t> rec_index;
   DevBuf<char> rec_stage;    // fast / sq16 launches: one staging buffer the packed rows unpack into
   DevBuf<double> sum_agent, sum_scen;  // p2pmg_episode_summary: [A][16] and [S][16], allocated on first use
+  // p2pmg_day_profile: the four outputs of the last call ([G][P][N][16], [G][P][N][8], [G][P][4], [G][P][2]) and
+  // the uploaded labels [S]; allocated or grown on first use, re-initialised on the stream at every call
+  DevBuf<unsigned long long> dp_sums, dp_csums;
+  DevBuf<uint32_t> dp_ext, dp_cext;
+  DevBuf<int32_t> dp_labels;
   // the table digests (p2pmg_table_stats & co.): block partials and folded results of the last call, and
   // the packed-policy snapshot [n_tables][n_states] u8 of p2pmg_policy_mark; all allocated on first use
   DevBuf<double> td_part, td_out;

@@ -296,6 +296,23 @@ struct SummaryParams {
 };
 // summary_agent_kernel then summary_scenario_kernel (which reads agent_out) on the stream
 hipError_t launch_episode_summary(const SummaryParams& p, hipStream_t stream);
+// p2pmg_day_profile (p2pmg_dayprof.hip): the last launch's records reduced over scenarios, per (group,
+// slot = t % P, agent position).  The launch shape is a DayProfPlan's (p2pmg_dayprof.h), by value here.
+struct DayProfParams {
+  SummaryParams rec;          // the records (agent_out and scen_out unused)
+  int G, P, t0, t1, s0, s1;   // groups, slots, the half-open step and scenario ranges
+  const int32_t* labels;      // [S] group of each scenario, -1: left out; null: every scenario in group 0
+  int lds, fold, tile_slots, tile_agents, n_tiles, tiles_per_run, slice_steps, n_slices;
+  size_t tile_bytes;
+  int com_slice_steps, com_n_slices;  // dayprof_community_kernel: steps per workgroup and slices of the range
+  unsigned long long* sums;   // [G][P][N][16] int64 sums (two's complement adds)
+  uint32_t* ext;              // [G][P][N][8] ordered images of the f32 extrema; dayprof_decode_kernel turns them into f32 in place
+  unsigned long long* com_sums;  // [G][P][4]
+  uint32_t* com_ext;          // [G][P][2]
+};
+// init (sums 0, extrema +inf / -inf), dayprof_agent_kernel, dayprof_community_kernel, decode, on the stream;
+// an empty step or scenario range launches init and decode only
+hipError_t launch_day_profile(const DayProfParams& p, hipStream_t stream);
 // the table digests (p2pmg_tables.hip): p2pmg_table_stats, p2pmg_greedy_policy, p2pmg_policy_mark and
 // p2pmg_policy_changes are one pass over `count` padded tables with different outputs switched on
 constexpr int kTableStats = 8;  // P2PMG_TABLE_STATS

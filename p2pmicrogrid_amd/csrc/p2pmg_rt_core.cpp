@@ -8,6 +8,7 @@
 #include <new>
 
 #include "p2pmg_ctx.h"
+#include "p2pmg_dayprof.h"
 
 using namespace p2pmg::rt;
 using p2pmg::kEnvStride;
@@ -417,10 +418,10 @@ int p2pmg_get_record(p2pmg_ctx* c, int which, void* host) {
   return download(c, {{host, src, bytes}});
 }
 
-int p2pmg_episode_summary(p2pmg_ctx* c, double* per_agent, double* per_scenario) {
-  if (!c) return P2PMG_E_INVALID;
-  if (!per_agent && !per_scenario) return fail(c, P2PMG_E_INVALID, "episode_summary: both outputs are null");
-  if (c->last.kernel.empty()) return fail(c, P2PMG_E_STATE, "episode_summary: no episode has run (cost, grid, p2p, t_in and action records are needed)");
+// What the post-passes over the last launch's records share (p2pmg_episode_summary, p2pmg_day_profile):
+// the launch recorded P2PMG_SUMMARY_RECORDS (else P2PMG_E_STATE naming what is missing), and where they lie.
+static int record_params(p2pmg_ctx* c, const std::string& who, p2pmg::SummaryParams* out) {
+  if (c->last.kernel.empty()) return fail(c, P2PMG_E_STATE, who + ": no episode has run (cost, grid, p2p, t_in and action records are needed)");
   const int missing = P2PMG_SUMMARY_RECORDS & ~c->last.mask;
   if (missing) {
     static const struct { int bit; const char* name; } names[] = {{P2PMG_REC_COST, "cost"}, {P2PMG_REC_GRID, "grid"},
@@ -429,11 +430,8 @@ int p2pmg_episode_summary(p2pmg_ctx* c, double* per_agent, double* per_scenario)
     std::string list;
     for (const auto& n : names)
       if (missing & n.bit) list += (list.empty() ? "" : ", ") + std::string(n.name);
-    return fail(c, P2PMG_E_STATE, "episode_summary: the last episode launch did not record " + list);
+    return fail(c, P2PMG_E_STATE, who + ": the last episode launch did not record " + list);
   }
-  const size_t A = (size_t)c->A, S = (size_t)c->S;
-  if (!c->sum_agent) HIP_TRY(c, c->sum_agent.alloc(A * P2PMG_SUMMARY_FIELDS));
-  if (!c->sum_scen) HIP_TRY(c, c->sum_scen.alloc(S * P2PMG_SUMMARY_FIELDS));
   p2pmg::SummaryParams p{};
   p.S = c->S;
   p.N = c->N;
@@ -454,10 +452,22 @@ int p2pmg_episode_summary(p2pmg_ctx* c, double* per_agent, double* per_scenario)
   p.prof = c->prof;
   p.hp_lv = c->hp_lv;
   p.thermal = c->thermal;
+  if (p.packed ? !p.rec_pack : (!p.cost || !p.grid || !p.p2p || !p.tin || !p.action || (p.has_reward && !p.reward)))
+    return fail(c, P2PMG_E_STATE, who + ": no record buffer");
+  *out = p;
+  return P2PMG_OK;
+}
+
+int p2pmg_episode_summary(p2pmg_ctx* c, double* per_agent, double* per_scenario) {
+  if (!c) return P2PMG_E_INVALID;
+  if (!per_agent && !per_scenario) return fail(c, P2PMG_E_INVALID, "episode_summary: both outputs are null");
+  p2pmg::SummaryParams p{};
+  RC_TRY(record_params(c, "episode_summary", &p));
+  const size_t A = (size_t)c->A, S = (size_t)c->S;
+  if (!c->sum_agent) HIP_TRY(c, c->sum_agent.alloc(A * P2PMG_SUMMARY_FIELDS));
+  if (!c->sum_scen) HIP_TRY(c, c->sum_scen.alloc(S * P2PMG_SUMMARY_FIELDS));
   p.agent_out = c->sum_agent;
   p.scen_out = c->sum_scen;
-  if (p.packed ? !p.rec_pack : (!p.cost || !p.grid || !p.p2p || !p.tin || !p.action || (p.has_reward && !p.reward)))
-    return fail(c, P2PMG_E_STATE, "episode_summary: no record buffer");
   HIP_TRY(c, p2pmg::launch_episode_summary(p, c->stream));
   if (per_agent)
     HIP_TRY(c, hipMemcpyAsync(per_agent, c->sum_agent, A * P2PMG_SUMMARY_FIELDS * sizeof(double), hipMemcpyDeviceToHost,
@@ -465,6 +475,64 @@ int p2pmg_episode_summary(p2pmg_ctx* c, double* per_agent, double* per_scenario)
   if (per_scenario)
     HIP_TRY(c, hipMemcpyAsync(per_scenario, c->sum_scen, S * P2PMG_SUMMARY_FIELDS * sizeof(double),
                               hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return P2PMG_OK;
+}
+
+int p2pmg_day_profile_shape(p2pmg_ctx* c, const p2pmg_day_profile_args* args, int32_t* G, int32_t* P) {
+  if (!c) return P2PMG_E_INVALID;
+  p2pmg::DayProfRange r;
+  if (const char* bad = p2pmg::dayprof_resolve(args, c->T, c->S, &r)) return fail(c, P2PMG_E_INVALID, std::string("day_profile: ") + bad);
+  if (G) *G = r.G;
+  if (P) *P = r.P;
+  return P2PMG_OK;
+}
+
+// P2PMG_DAYPROF_TILE_BYTES, read at every call: the LDS a workgroup of dayprof_agent_kernel may use
+static size_t dayprof_tile_budget() {
+  const char* v = getenv("P2PMG_DAYPROF_TILE_BYTES");
+  if (!v || !*v) return p2pmg::kDayProfTileDefault;
+  char* end = nullptr;
+  const unsigned long long n = strtoull(v, &end, 10);
+  return end == v || *end ? p2pmg::kDayProfTileDefault : (size_t)n;
+}
+
+int p2pmg_day_profile(p2pmg_ctx* c, const p2pmg_day_profile_args* args, int64_t* sums, float* extrema, int64_t* com_sums,
+                      float* com_extrema) {
+  if (!c) return P2PMG_E_INVALID;
+  if (!sums && !extrema && !com_sums && !com_extrema) return fail(c, P2PMG_E_INVALID, "day_profile: all four outputs are null");
+  p2pmg::DayProfParams p{};
+  RC_TRY(record_params(c, "day_profile", &p.rec));
+  p2pmg::DayProfRange r;
+  if (const char* bad = p2pmg::dayprof_resolve(args, c->T, c->S, &r)) return fail(c, P2PMG_E_INVALID, std::string("day_profile: ") + bad);
+  const int steps = r.t1 - r.t0, scen = r.s1 - r.s0;
+  const std::vector<int64_t> hist = p2pmg::dayprof_histogram(args->groups, r);
+  if (const char* bad = p2pmg::dayprof_check_samples(hist.data(), r.G, steps, r.P))
+    return fail(c, P2PMG_E_INVALID, std::string("day_profile: ") + bad);
+  const size_t crows = (size_t)r.G * (size_t)r.P, rows = crows * (size_t)c->N;
+  HIP_TRY(c, c->dp_sums.grow(rows * p2pmg::kDayProfSums));
+  HIP_TRY(c, c->dp_ext.grow(rows * p2pmg::kDayProfExtrema));
+  HIP_TRY(c, c->dp_csums.grow(crows * p2pmg::kDayProfComSums));
+  HIP_TRY(c, c->dp_cext.grow(crows * p2pmg::kDayProfComExtrema));
+  if (r.labelled) {
+    HIP_TRY(c, c->dp_labels.grow((size_t)c->S));
+    HIP_TRY(c, hipMemcpyAsync(c->dp_labels, args->groups, (size_t)c->S * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  }
+  p.G = r.G, p.P = r.P, p.t0 = r.t0, p.t1 = r.t1, p.s0 = r.s0, p.s1 = r.s1;
+  p.labels = r.labelled ? c->dp_labels.get() : nullptr;
+  if (steps > 0 && scen > 0) {
+    const p2pmg::DayProfPlan plan = p2pmg::dayprof_plan(r.G, r.P, c->N, (int64_t)scen * c->N, steps, dayprof_tile_budget());
+    p.lds = plan.lds, p.fold = plan.fold, p.tile_slots = plan.tile_slots, p.tile_agents = plan.tile_agents;
+    p.n_tiles = plan.n_tiles, p.tiles_per_run = plan.tiles_per_run, p.slice_steps = plan.slice_steps, p.n_slices = plan.n_slices;
+    p.tile_bytes = plan.tile_bytes;
+  }
+  p.sums = c->dp_sums, p.ext = c->dp_ext, p.com_sums = c->dp_csums, p.com_ext = c->dp_cext;
+  HIP_TRY(c, p2pmg::launch_day_profile(p, c->stream));
+  const struct { void* host; const void* dev; size_t bytes; } outs[] = {
+      {sums, c->dp_sums, rows * p2pmg::kDayProfSums * 8}, {extrema, c->dp_ext, rows * p2pmg::kDayProfExtrema * 4},
+      {com_sums, c->dp_csums, crows * p2pmg::kDayProfComSums * 8}, {com_extrema, c->dp_cext, crows * p2pmg::kDayProfComExtrema * 4}};
+  for (const auto& o : outs)
+    if (o.host) HIP_TRY(c, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return P2PMG_OK;
 }

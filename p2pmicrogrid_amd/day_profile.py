@@ -6,9 +6,9 @@ plot_grid_load (data_analysis.py: mean indoor temperature, heat-pump duty, cost 
 day).  One row per (group g, slot p = t % P, agent position i) and one per (g, p) for the community.
 
 This module is the HOST form: ``from_records`` reduces records that are already in host memory, which is where
-``CommunityMicrogrid.run()`` and ``run_days()`` put them anyway.  It is no substitute for a device pass on a
-large batch (get_records of a 125,000 x 16 batch is 0.77 GB per record): DeviceCommunityBatch has no
-day_profile call.
+``CommunityMicrogrid.run()`` and ``run_days()`` put them anyway.  On a large batch (get_records of a
+125,000 x 16 batch is 0.77 GB per record) use DeviceCommunityBatch.day_profile(), the device pass with this
+definition (p2pmg_day_profile): it returns the same four arrays bit for bit.
 
 The four arrays, bit for bit:
   sums        [G, P, N, 16] i64  per sample (s, t) of the row (SUM_FIELDS, fix shifts SUM_SHIFTS): 1; fix(cost, 28);

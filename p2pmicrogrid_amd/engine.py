@@ -601,6 +601,39 @@ class DeviceCommunityBatch:
         return {"agent": {n: np.ascontiguousarray(ag[..., j]) for j, n in enumerate(SUMMARY_FIELDS)},
                 "scenario": {n: np.ascontiguousarray(sc[:, j]) for j, n in enumerate(SUMMARY_FIELDS)}}
 
+    def day_profile(self, period: Optional[int] = None, steps: Optional[Sequence[int]] = None,
+                    scenarios: Optional[Sequence[int]] = None, groups=None, n_groups: Optional[int] = None,
+                    as_dict: bool = False, kwh: bool = False):
+        """The last episode launch's records reduced over scenarios on the device (p2pmg_day_profile):
+        (sums [G, P, N, 16] i64, extrema [G, P, N, 8] f32, com_sums [G, P, 4] i64, com_extrema [G, P, 2] f32),
+        bit for bit day_profile.from_records of the same records, so day_profile.merge and
+        distributed.merge_day_profiles take them as they are.  Arguments as from_records': period None or 0 = T
+        (no folding); steps, scenarios = (first, stop), None = all; groups [S] labels in [-1, n_groups), None =
+        one group; n_groups None = max(label) + 1.  The launch must have recorded SUMMARY_RECORDS.
+        as_dict=True: day_profile.as_dict of the arrays, kwh=True with the mean powers as kWh per step."""
+        from . import day_profile as dayprof
+        t0, n_t = (0, -1) if steps is None else (int(steps[0]), int(steps[1]) - int(steps[0]))
+        s0, n_s = (0, -1) if scenarios is None else (int(scenarios[0]), int(scenarios[1]) - int(scenarios[0]))
+        if n_t < 0 and steps is not None or n_s < 0 and scenarios is not None:
+            raise ValueError("day_profile: a range's stop lies before its first")
+        lab = None
+        if groups is not None:
+            lab = np.ascontiguousarray(np.asarray(groups).astype(np.int64).reshape(-1))
+            if lab.shape != (self.S,):
+                raise ValueError("day_profile: one label per scenario")
+            lab = np.clip(lab, -2, np.iinfo(np.int32).max).astype(np.int32)  # the library refuses what lies outside [-1, G)
+        args = _lib.DayProfileArgs(int(period or 0), t0, n_t, s0, n_s, 0 if n_groups is None else max(int(n_groups), 1),
+                                   None if lab is None else lab.ctypes.data)
+        G, P = C.c_int32(0), C.c_int32(0)
+        self._chk(self.L.p2pmg_day_profile_shape(self._ctx, C.byref(args), C.byref(G), C.byref(P)), "day_profile")
+        G, P = int(G.value), int(P.value)
+        out = (np.empty((G, P, self.N, 16), np.int64), np.empty((G, P, self.N, 8), F32), np.empty((G, P, 4), np.int64),
+               np.empty((G, P, 2), F32))
+        self._chk(self.L.p2pmg_day_profile(self._ctx, C.byref(args), *(a.ctypes.data for a in out)), "day_profile")
+        if not as_dict:
+            return out
+        return dayprof.as_dict(*out, energy_scale=float(self.cfg.time_slot) / 60.0 * 1e-3 if kwh else 1.0)
+
     def episode_reward(self) -> np.ndarray:
         out = np.empty(self.S, F32)
         self._chk(self.L.p2pmg_get_episode_reward(self._ctx, out), "episode_reward")
