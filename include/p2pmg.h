@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag, p2pmg_set_learning, p2pmg_get_learning, p2pmg_run_episodes_eps, p2pmg_table_stats, p2pmg_greedy_policy, p2pmg_policy_mark, p2pmg_policy_changes, n_actions = 2 table-only contexts, p2pmg_sparse_count, p2pmg_get_q_sparse, p2pmg_set_q_sparse, p2pmg_copy_q, p2pmg_day_profile_shape, p2pmg_day_profile) */
+#define P2PMG_ABI_VERSION 9  /* 3: p2pmg_episode_args.next_epsilon; 4: P2PMG_FLAG_NEXT_EPSILON, p2pmg_prepass_stats, per-network Adam steps; 5: p2pmg_collective_ms; 6: DQN gradient segments, p2pmg_dqn_set_exchange, p2pmg_dqn_grad_layout; 7: p2pmg_run_episodes, p2pmg_get_episode_rewards; 8: N up to 64 and any R, P2PMG_FLAG_TILE_KERNEL; 9: p2pmg_set_thermal, p2pmg_get_thermal, p2pmg_rc_step_ex, p2pmg_get_hp_levels (added since without a bump: P2PMG_SHARED_ROLE, p2pmg_episode_summary, p2pmg_chain_lag, p2pmg_set_learning, p2pmg_get_learning, p2pmg_run_episodes_eps, p2pmg_table_stats, p2pmg_greedy_policy, p2pmg_policy_mark, p2pmg_policy_changes, n_actions = 2 table-only contexts, p2pmg_sparse_count, p2pmg_get_q_sparse, p2pmg_set_q_sparse, p2pmg_copy_q, p2pmg_day_profile_shape, p2pmg_day_profile, P2PMG_DQN_POLICY_SET, p2pmg_dqn_set_policy_nets, p2pmg_dqn_get_policy_nets, p2pmg_dqn_run_greedy) */
 
 typedef struct p2pmg_ctx p2pmg_ctx;
 
@@ -695,6 +695,51 @@ int p2pmg_dqn_map_stats(p2pmg_ctx* ctx, int which, int first, int count, double*
 int p2pmg_dqn_policy_mark(p2pmg_ctx* ctx, int which);
 int p2pmg_dqn_policy_changes(p2pmg_ctx* ctx, int which, int first, int count, int64_t* changed /* [count] */,
                              int remark);
+
+/* DQN evaluation: frozen networks, one launch per greedy episode.  p2pmg_run_episode(P2PMG_MODE_GREEDY) on a
+ * DQN context is T act launches, each streaming every agent's network again although nothing changes a
+ * weight.  p2pmg_dqn_run_greedy runs the same T greedy env steps in ONE launch of
+ * dqn_greedy_episode_kernel (one workgroup per scenario, the time loop inside; a wave loads its agent's
+ * network once, T_in / T_m stay on the chip between steps), on the context's own networks or on a POLICY
+ * SET: M networks and a map agent -> network that the context owns on the device beside the learner's
+ * online, target and Adam arrays.  No training call reads or writes the set, so one community of N trained
+ * networks is evaluated over S scenarios (days) at once with the role map a -> a % N; p2pmg_create keeps
+ * refusing P2PMG_SHARED_ROLE with the DQN learner (no per-role network is TRAINED).
+ *
+ * p2pmg_dqn_set_policy_nets uploads count networks [count][P2PMG_DQN_PARAMS] and the map net_of [A], values
+ * in [0, count).  The whole map is checked on the host before anything is uploaded: a value out of range is
+ * P2PMG_E_INVALID and leaves the current set as it was.  net_of == NULL is the default map: a % count (role
+ * i of every scenario) when count == N, the identity when count == A, all 0 when count == 1, and otherwise
+ * P2PMG_E_INVALID.  count == 0 drops the set (weights and net_of are then ignored); count < 0 or NULL
+ * weights: P2PMG_E_INVALID.  p2pmg_dqn_get_policy_nets returns the set: *count (0: none; nothing else is
+ * then written) and, where non-NULL, the weights and the map in use.
+ *
+ * p2pmg_dqn_run_greedy: source = P2PMG_DQN_ONLINE or P2PMG_DQN_TARGET (the context's own array: agent a's
+ * network, or network 0 of a shared context) or P2PMG_DQN_POLICY_SET; record = the P2PMG_REC_* mask of
+ * REWARD, COST, GRID, P2P, TEMP and ACTION (same buffers and layouts as an episode's).  Stream-ordered and
+ * timed like an episode: p2pmg_get_record, p2pmg_get_episode_reward, p2pmg_episode_summary,
+ * p2pmg_day_profile and p2pmg_last_kernel_ms work after it, and p2pmg_last_kernel reads
+ * "dqn_greedy_episode_kernel<N>".  Results, records, final temperatures and episode rewards are, bit for
+ * bit, those of p2pmg_run_episode(P2PMG_MODE_GREEDY) on a per-agent DQN context whose network a is a copy
+ * of the mapped network: every value is formed by the act kernels' expression sequence (the act_q order
+ * above, the sequential sums over j, _divide_power, the pair exchange, cost, reward and RC update at the
+ * agent's own thermal values and heat-pump levels, sum_t mean_i r in step order).  Any N in 1..64, any R
+ * with R + 1 <= 4096, n_env 1 or S.  Greedy only: no RNG, no replay codes, no replay-memory append; every
+ * weight array, the Adam step counts, the replay rings, their `added` counts and the replay-code state
+ * are left as they were.  T_in / T_m move as in any episode.
+ * Which form to prefer (MI355X, HIP events, profiles/dqn_eval/README.md): with per-agent networks, or a policy
+ * set, this call: 1.4x to 2.0x faster than the stepwise episode at every shape measured, 5 to 4096
+ * scenarios, one day to one year.  For ONE SHARED network over thousands of agents prefer
+ * p2pmg_run_episode(P2PMG_MODE_GREEDY): its MFMA act kernel forwards 16 agents per workgroup on the matrix
+ * cores and was 2.5x faster than this call's one wave per agent at configs[4]'s shape (4096 x 2, T = 96).
+ * Errors: NULL context P2PMG_E_INVALID; tabular context, or before p2pmg_dqn_setup, P2PMG_E_STATE;
+ * P2PMG_DQN_POLICY_SET without a set, or before env, profiles and agent params are set, P2PMG_E_STATE;
+ * P2PMG_REC_LOSS (or any other bit outside the six records) or an unknown source P2PMG_E_INVALID. */
+#define P2PMG_DQN_POLICY_SET 4
+int p2pmg_dqn_set_policy_nets(p2pmg_ctx* ctx, int count, const float* weights /* [count][P2PMG_DQN_PARAMS] */,
+                              const int32_t* net_of /* [A], values in [0, count), or NULL */);
+int p2pmg_dqn_get_policy_nets(p2pmg_ctx* ctx, int* count, float* weights /* or NULL */, int32_t* net_of /* or NULL */);
+int p2pmg_dqn_run_greedy(p2pmg_ctx* ctx, int source, int record);
 
 /* Shared network over several ranks (config 5): the gradient segments of every rank are gathered
  * once per env step, then every rank sums all of them in global segment order and takes the same

@@ -36,14 +36,14 @@ UNITS = [
     *[("p2pmg_fast.hip", f"P2PMG_FAST_SLICE={k}", [], f"fast_{k}.o") for k in range(4)],
     ("p2pmg_sq16.hip", None, SQ16_FLAGS, "sq16.o"),
     *[("p2pmg_general.hip", f"P2PMG_GENERAL_SLICE={k}", [], f"general_{k}.o") for k in range(9)],
-    *[(f"p2pmg_dqn_{u}.hip", None, [], f"p2pmg_dqn_{u}.o") for u in ("act", "act_shared", "train", "shared")],
+    *[(f"p2pmg_dqn_{u}.hip", None, [], f"p2pmg_dqn_{u}.o") for u in ("act", "act_shared", "train", "shared", "eval")],
     ("p2pmg_dqn_map.hip", None, [], "p2pmg_dqn_map.o"),
     ("p2pmg_summary.hip", None, [], "p2pmg_summary.o"),
     ("p2pmg_dayprof.hip", None, [], "p2pmg_dayprof.o"),
     ("p2pmg_tables.hip", None, [], "p2pmg_tables.o"),
     ("p2pmg_host.cpp", None, [], "p2pmg_host.o"),
     *[(f"p2pmg_rt_{u}.cpp", None, [], f"p2pmg_rt_{u}.o") for u in ("core", "episode", "tables", "comm", "probe", "dqn",
-                                                                     "dqn_map")],
+                                                                     "dqn_map", "dqn_eval")],
     ("p2pmg_plan.cpp", None, [], "p2pmg_plan.o"),
     ("p2pmg_sparse.cpp", None, [], "p2pmg_sparse.o"),
     ("p2pmg_dayprof.cpp", None, [], "p2pmg_dayprof_host.o"),

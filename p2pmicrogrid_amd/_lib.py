@@ -20,6 +20,7 @@ MODE_TRAIN, MODE_GREEDY, MODE_FILL = 0, 1, 2
 LEARNER_TABULAR, LEARNER_DQN = 0, 1
 SHARED_ROLE = 2  # Config.shared_q: one table per agent position (P2PMG_SHARED_ROLE)
 DQN_ONLINE, DQN_TARGET, DQN_ADAM_M, DQN_ADAM_V = 0, 1, 2, 3
+DQN_POLICY_SET = 4  # p2pmg_dqn_run_greedy's source: the evaluation policy set (P2PMG_DQN_POLICY_SET)
 DQN_PARAMS = 4609
 RNG_REPLAY, RNG_PHILOX = 0, 1
 REC = {"reward": 1, "cost": 2, "grid": 4, "p2p": 8, "t_in": 16, "action": 32, "index": 64, "loss": 128}
@@ -54,6 +55,7 @@ EXPORTS = [
     "p2pmg_dqn_policy_changes",
     "p2pmg_sparse_count", "p2pmg_get_q_sparse", "p2pmg_set_q_sparse", "p2pmg_copy_q",
     "p2pmg_day_profile_shape", "p2pmg_day_profile",
+    "p2pmg_dqn_set_policy_nets", "p2pmg_dqn_get_policy_nets", "p2pmg_dqn_run_greedy",
 ]
 
 
@@ -197,6 +199,9 @@ def _declare(lib):
         "p2pmg_dqn_map_stats": ([vp, i32, i32, i32, vp], i32),      # [count][DQN_MAP_STATS] f64
         "p2pmg_dqn_policy_mark": ([vp, i32], i32),
         "p2pmg_dqn_policy_changes": ([vp, i32, i32, i32, vp, i32], i32),  # changed [count] i64
+        "p2pmg_dqn_set_policy_nets": ([vp, i32, vp, vp], i32),      # count, weights [count][DQN_PARAMS] f32, net_of [A] i32 or NULL
+        "p2pmg_dqn_get_policy_nets": ([vp, C.POINTER(C.c_int), vp, vp], i32),
+        "p2pmg_dqn_run_greedy": ([vp, i32, i32], i32),              # source, record mask
         "p2pmg_prepass_stats": ([vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], i32),
         "p2pmg_chain_lag": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int)], i32),
         "p2pmg_dqn_get_net_steps": ([vp, i32, i32, vp], i32),

@@ -329,7 +329,7 @@ class CommunityMicrogrid:
         ``profile=True`` returns (that list, the mean day): {"agent": {name: [P, N] f64}, "community":
         {name: [P] f64}}, the days reduced per time slot and agent (day_profile.from_records on the records this
         call returns anyway, the days being the launch's scenarios; ``period``: slots, None = T).
-        Tabular communities only."""
+        Tabular communities only; evaluate_days takes DQN communities too (and comes here for tabular ones)."""
         if self._rule or self._dqn:
             raise NotImplementedError("run_days needs tabular (QAgent) agents: per-role tables hold Q-tables, "
                                       "and a RuleAgent community has no policy to share")
@@ -364,6 +364,12 @@ class CommunityMicrogrid:
             totals = eng.episode_summary()["agent"] if summary else None
         finally:
             eng.close()
+        return self._days_out(r, t_in, t_m, totals, levels, load, pv, par, profile, period)
+
+    def _days_out(self, r, t_in, t_m, totals, levels, load, pv, par, profile, period):
+        """What run_days / evaluate_days return, from the records [T, D, N] of the one launch, the final
+        temperatures [D, N], the per-agent totals (or None) and the inputs the profile needs."""
+        D, N = t_in.shape
         max_power = np.array([a.heating.hp.max_power for a in self.agents])
         out = []
         for d in range(D):
@@ -376,6 +382,46 @@ class CommunityMicrogrid:
             arrays = dayprof.from_records(r, np.broadcast_to(levels, (D, N, 3)), load, pv, par[..., 1], par[..., 2], period=period)
             return out, _drop_groups(dayprof.as_dict(*arrays))
         return out
+
+    def evaluate_days(self, days, summary: bool = False, profile: bool = False, period: Optional[int] = None):
+        """run() of this community over several days in ONE greedy launch, for tabular and DQN communities:
+        the arguments and the return value of run_days, each day bit for bit what run() computes from that
+        day's inputs.  Tabular communities: run_days.  DQN communities: a DeviceDQNBatch with one scenario
+        per day whose policy set is the agents' N online networks with the role map (agent i of every day
+        reads network i), run by run_greedy("policy"): dqn_greedy_episode_kernel, the whole evaluation
+        in one launch instead of T act launches per day.  The agents' networks are read, nothing else
+        of the community changes; nothing is trained or drawn."""
+        if not self._dqn:
+            return self.run_days(days, summary=summary, profile=profile, period=period)
+        D, N = len(days), len(self.agents)
+        if D == 0:
+            return ([], None) if profile else []
+        T = len(np.asarray(days[0]["time"]).reshape(-1))
+
+        def stack(key, shape):
+            return np.stack([np.asarray(d[key], F32).reshape(shape) for d in days])
+        time_f, t_out = stack("time", (T,)), stack("t_out", (T,))
+        from .dqn import DeviceDQNBatch
+        eng = DeviceDQNBatch(D, N, self._rounds, T, device=self._device, capacity=32, init_seed=None)
+        try:
+            eng.set_policy_nets(np.stack([a.actor.q_network.flat_weights() for a in self.agents]))
+            eng.set_env(time_f, t_out, *price_table(time_f))
+            load, pv = stack("load", (N, T)), stack("pv", (N, T))
+            eng.set_profiles(load, pv)
+            eng.set_max_in(np.broadcast_to(np.array([F32(a.max_in) for a in self.agents], F32), (D, N)))
+            levels, params = thermal_arrays(self.agents)
+            eng.set_hp_levels(np.broadcast_to(levels, (D, N, 3)))
+            par = np.broadcast_to(params, (D, N, 4))
+            eng.set_thermal(par[..., 0], cop=par[..., 3], lower=par[..., 1], upper=par[..., 2])
+            eng.set_temperatures(stack("t_in", (N,)), stack("t_m", (N,)))
+            rec = ("grid", "p2p", "cost", "t_in", "action")
+            eng.run_greedy("policy", record=rec)
+            r = eng.get_records(rec)
+            t_in, t_m = eng.get_temperatures()
+            totals = eng.episode_summary()["agent"] if summary else None
+        finally:
+            eng.close()
+        return self._days_out(r, t_in, t_m, totals, levels, load, pv, par, profile, period)
 
     def _run_rule(self) -> Tuple[np.ndarray, np.ndarray]:
         """run() of a RuleAgent community: one rule_episode_kernel launch (R = 0)."""
@@ -676,11 +722,12 @@ def load_and_run(con=None, is_testing: bool = False, analyse: bool = True) -> Di
 
 
 def load_and_run_batched(con=None, is_testing: bool = False) -> Dict[int, Dict[str, np.ndarray]]:
-    """load_and_run with every day in ONE greedy launch (CommunityMicrogrid.run_days): the same per-day
+    """load_and_run with every day in ONE greedy launch (CommunityMicrogrid.evaluate_days): the same per-day
     results, bit for bit, the same DB rows and the same np.random consumption.  The day-by-day loop
     draws, per day, community.reset()'s T0 and then _set_day_profiles' scales and resets; the greedy
     launch draws nothing, so all of that is drawn first, day after day in that order, and each day's
-    inputs are kept for the launch.  Tabular communities only."""
+    inputs are kept for the launch.  Tabular (per-role tables) and DQN (a policy set of the agents'
+    networks) communities."""
     setting = setting_name()
     community = get_rl_based_community(setup.nr_agents, homogeneous=setup.homogeneous)
     for agent in community.agents:
@@ -705,7 +752,7 @@ def load_and_run_batched(con=None, is_testing: bool = False) -> Dict[int, Dict[s
                        "t_in": np.array([a.heating.temperature[0] for a in community.agents], F32),
                        "t_m": np.array([a.heating.building_mass_temperature[0] for a in community.agents], F32)})
         held.append((day_env, [(a._load, a.pv.pv.production) for a in community.agents]))
-    results = community.run_days(inputs)
+    results = community.evaluate_days(inputs)
     out = {}
     for day, (day_env, profiles), res in zip(days, held, results):
         # the community as run() leaves it after this day: what save_community_results reads

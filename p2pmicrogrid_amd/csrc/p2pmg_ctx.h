@@ -222,6 +222,12 @@ struct p2pmg_ctx : p2pmg::PlanFacts {
   DevBuf<double> map_out;
   DevBuf<long long> map_cout;
   DevBuf<uint8_t> map_snap;
+  // the evaluation policy set (p2pmg_dqn_set_policy_nets): pol_count networks and the agent -> network map,
+  // read by p2pmg_dqn_run_greedy(P2PMG_DQN_POLICY_SET) alone; no training call reads or writes them
+  DevBuf<float> d_pol;          // [pol_count][kNetStride]
+  DevBuf<int32_t> d_pol_map;    // [A]
+  std::vector<int32_t> h_pol_map;
+  int pol_count = 0;            // 0: no set
   std::vector<int64_t> d_steps;  // Adam iterations done, per network (agent.py:310: one optimizer per agent)
   DevBuf<float> d_lr;      // [T][n_nets] per-network step sizes of one episode when the counts differ
   std::vector<float> h_lr;

@@ -1,6 +1,6 @@
 // p2pmg_dqn_ops.h — the MFMA, DPP and permlane helpers that define the summation order of the DQN
 // kernels (p2pmg_dqn_act.hip, p2pmg_dqn_act_shared.hip, p2pmg_dqn_train.hip, p2pmg_dqn_shared.hip: act,
-// train, forward; p2pmg_dqn_map.hip: the policy map).  One copy: the order of a
+// train, forward; p2pmg_dqn_eval.hip: the one-launch greedy episode; p2pmg_dqn_map.hip: the policy map).  One copy: the order of a
 // reduction below is part of the bit-for-bit contract with oracle/dqn.py (fmaf chain in k order for the
 // f32 MFMA, the pairwise tree of tree_sum for the lane sums).  Included inside the including unit's
 // anonymous namespace, after p2pmg_device.h.

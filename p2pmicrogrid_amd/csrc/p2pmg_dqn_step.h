@@ -1,5 +1,5 @@
 // p2pmg_dqn_step.h — the pieces of one DQN env step that more than one DQN unit needs
-// (p2pmg_dqn_act.hip, p2pmg_dqn_act_shared.hip, p2pmg_dqn_train.hip, p2pmg_dqn_shared.hip): the batch
+// (p2pmg_dqn_act.hip, p2pmg_dqn_act_shared.hip, p2pmg_dqn_train.hip, p2pmg_dqn_shared.hip, p2pmg_dqn_eval.hip): the batch
 // size, the replay sample draw, the act kernels' replayed codes and settlement, the one Adam / soft-update
 // rounding sequence (bit for bit oracle/dqn.py's) with the shared network's post-exchange step, and the
 // trace builds' phase stamp.  Included inside the including unit's anonymous namespace, after

@@ -169,6 +169,17 @@ constexpr int kActAdamSegs = 8;
 bool dqn_act_fuses_adam(const DqnParams& p);
 hipError_t launch_dqn_forward(const float* theta, int n, const float* x, float* q, hipStream_t stream);
 
+// the frozen-policy episode (p2pmg_dqn_eval.hip, p2pmg_dqn_run_greedy): T greedy env steps in one launch
+struct DqnEvalParams {
+  EpisodeParams e;           // as for a greedy dqn_act_kernel launch (mode, rng, codes unused)
+  const float* nets;         // [count][kNetStride] the networks the episode reads
+  const int32_t* net_of;     // [A] agent -> network of `nets`; null: the context's own arrays (one_net)
+  int one_net;               // net_of == null: 1 = every agent reads network 0, 0 = agent a reads network a
+  float* ep_acc;             // [S] left as the stepwise episode leaves it (= ep_reward)
+};
+// dqn_greedy_episode_kernel<N>: one workgroup per scenario, any N in 1..kMaxAgents
+hipError_t launch_dqn_greedy_episode(const DqnEvalParams& p, hipStream_t stream);
+
 // the DQN policy map (p2pmg_dqn_map.hip): p2pmg_dqn_policy_map, p2pmg_dqn_map_stats, p2pmg_dqn_policy_mark
 // and p2pmg_dqn_policy_changes are one pass over `count` networks and the states [g_begin, g_begin +
 // g_count) of the grid, with different outputs switched on

@@ -29,6 +29,7 @@ F32 = np.float32
 N_PARAMS = _lib.DQN_PARAMS
 WHICH = {"online": _lib.DQN_ONLINE, "target": _lib.DQN_TARGET, "adam_m": _lib.DQN_ADAM_M, "adam_v": _lib.DQN_ADAM_V}
 MAP_WHICH = {"online": _lib.DQN_ONLINE, "target": _lib.DQN_TARGET}  # arrays the policy map reads
+EVAL_SOURCES = {"online": _lib.DQN_ONLINE, "target": _lib.DQN_TARGET, "policy": _lib.DQN_POLICY_SET}  # run_greedy
 MODES = {"train": _lib.MODE_TRAIN, "greedy": _lib.MODE_GREEDY, "fill": _lib.MODE_FILL}
 ACTION_VALUES = np.array([0.0, 0.5, 1.0], dtype=F32)  # ActorModel.actions rl.py:153
 
@@ -44,6 +45,21 @@ def glorot_init(n_nets: int, seed: int = 0) -> np.ndarray:
         th[:, off:off + fi * fo] = rs.uniform(-lim, lim, size=(n_nets, fi * fo)).astype(F32)
         off += fi * fo + fo
     return th
+
+
+def default_net_map(count: int, n_scenarios: int, n_agents: int) -> np.ndarray:
+    """The map agent -> network of a policy set of ``count`` networks when none is given
+    (p2pmg_dqn_set_policy_nets with net_of = NULL): int32 [S * N], a % count (role i of every scenario) when
+    count == N, the identity when count == S * N, all 0 when count == 1; anything else raises.  Pure NumPy."""
+    A = int(n_scenarios) * int(n_agents)
+    if count == n_agents:
+        return (np.arange(A) % count).astype(np.int32)
+    if count == A:
+        return np.arange(A, dtype=np.int32)
+    if count == 1:
+        return np.zeros(A, np.int32)
+    raise ValueError(f"a policy set of {count} networks needs net_of: the default maps are for N = {n_agents}, "
+                     f"A = {A} or 1 networks")
 
 
 class DeviceDQNBatch(DeviceCommunityBatch):
@@ -172,6 +188,48 @@ class DeviceDQNBatch(DeviceCommunityBatch):
         if st != _lib.P2PMG_OK and self._xerr is not None:
             raise _lib.P2PMGError(f"run_episode: the gradient exchange raised {self._xerr!r}") from self._xerr
         self._chk(st, "run_episode")
+        self._recorded = mask
+
+    # ----------------------------------------------------------------- evaluation
+    def set_policy_nets(self, weights, net_of=None):
+        """The evaluation policy set: M frozen networks [M, 4609] and the map agent -> network [A] (or
+        [S, N]), held on the device beside the learner's arrays and read by run_greedy("policy") alone.
+        net_of=None: default_net_map (role a % N for M == N, the identity for M == A, all 0 for M == 1).
+        ``weights=None`` (or no rows) drops the set.  A map value outside [0, M) raises and changes nothing."""
+        if weights is None or np.size(weights) == 0:
+            self._chk(self.L.p2pmg_dqn_set_policy_nets(self._ctx, 0, None, None), "dqn_set_policy_nets")
+            return
+        w = np.ascontiguousarray(np.asarray(weights, dtype=F32).reshape(-1, N_PARAMS))
+        m = default_net_map(w.shape[0], self.S, self.N) if net_of is None else \
+            np.ascontiguousarray(np.asarray(net_of).reshape(-1).astype(np.int32))
+        if m.size != self.A:
+            raise ValueError(f"net_of needs one entry per agent ({self.A}), got {m.size}")
+        self._chk(self.L.p2pmg_dqn_set_policy_nets(self._ctx, w.shape[0], w.ctypes.data, m.ctypes.data),
+                  "dqn_set_policy_nets")
+
+    def policy_nets(self):
+        """(weights [M, 4609] f32, net_of [A] int32) of the policy set in use; None without one."""
+        n = C.c_int(0)
+        self._chk(self.L.p2pmg_dqn_get_policy_nets(self._ctx, C.byref(n), None, None), "dqn_get_policy_nets")
+        if n.value == 0:
+            return None
+        w = np.empty((n.value, N_PARAMS), F32)
+        m = np.empty(self.A, np.int32)
+        self._chk(self.L.p2pmg_dqn_get_policy_nets(self._ctx, C.byref(n), w.ctypes.data, m.ctypes.data),
+                  "dqn_get_policy_nets")
+        return w, m
+
+    def run_greedy(self, source: str = "online", record: Sequence[str] = ()):
+        """One greedy episode of T steps for every scenario in ONE launch (dqn_greedy_episode_kernel), on
+        the frozen networks of ``source``: "online" or "target" (this batch's own) or "policy" (the policy
+        set).  Bit for bit run_episode("greedy") on a per-agent batch holding the mapped networks; trains
+        and draws nothing, leaves the learner's state alone (asynchronous, stream-ordered)."""
+        if source not in EVAL_SOURCES:
+            raise ValueError(f"source must be one of {sorted(EVAL_SOURCES)}, not {source!r}")
+        mask = 0
+        for r in record:
+            mask |= _lib.REC[r]
+        self._chk(self.L.p2pmg_dqn_run_greedy(self._ctx, EVAL_SOURCES[source], mask), "dqn_run_greedy")
         self._recorded = mask
 
     # ----------------------------------------------------------------- object-API primitives
