@@ -526,7 +526,7 @@ int p2pmg_get_thermal(p2pmg_ctx* ctx, float* params);
  * config, so a context that never calls this computes the same bits as with the broadcast constants.
  * A shared-table N = 16 context with values set here runs the general kernel's shared-table form
  * instead of episode_sq16_kernel (same results, bit for bit) until the all-NULL call restores the
- * config's.  DQN contexts: P2PMG_E_UNSUPPORTED (the DQN's gamma is p2pmg_dqn_config.gamma). */
+ * config's.  DQN contexts: P2PMG_E_UNSUPPORTED (their call is p2pmg_dqn_set_learning). */
 int p2pmg_set_learning(p2pmg_ctx* ctx, const double* alpha, const double* gamma, const float* penalty_weight);
 /* the values in use, each [A]; any output may be NULL */
 int p2pmg_get_learning(p2pmg_ctx* ctx, double* alpha, double* gamma, float* penalty_weight);
@@ -628,6 +628,39 @@ int p2pmg_dqn_set_buffer(p2pmg_ctx* ctx, int first, int count, const float* host
 int p2pmg_dqn_forward(p2pmg_ctx* ctx, int net, int n, const float* x, float* q);
 /* Trainer._train + update_targets (rl.py:307-359) of one network on a given batch [32][10] */
 int p2pmg_dqn_train_batch(p2pmg_ctx* ctx, int net, const float* batch, float* loss);
+/* Per-network learner constants of the DQN learner: each DQNAgent's own Trainer(gamma, tau, Adam(learning_rate))
+ * (agent.py:306-311, rl.py:253-266), the first kernel's gradient clip (rl.py:329) and the comfort weight of each
+ * agent's reward (agent.py:225-232).  gamma, tau, lr and clip are [n_nets] (A rows for per-agent networks, one row
+ * for the shared network); penalty_weight is [A], per AGENT, in either case.  A NULL pointer leaves that field as
+ * it is; all five NULL restore what p2pmg_dqn_setup filled in: every row from p2pmg_dqn_config, every weight from
+ * config.penalty_weight.  The whole input is checked on the host before anything is uploaded: values must be
+ * finite with 0 <= gamma <= 1, 0 <= tau <= 1, lr >= 0, clip > 0 and penalty_weight >= 0, else P2PMG_E_INVALID
+ * (p2pmg_last_error names the network or agent) and the state stays untouched.  A tabular context, or a call
+ * before p2pmg_dqn_setup: P2PMG_E_STATE.
+ * Each value reaches the kernels as the f32 cast of the double (tau_c = 1.0f - (float)tau per row); betas and
+ * adam_eps stay the context's.  dqn_train_kernel reads gamma (the target), clip (the first kernel's gradient)
+ * and tau (the soft update): for per-agent networks each workgroup loads its network's row as wave-uniform
+ * scalars, and only when the rows differ (equal rows take the scalar kernel arguments: the same bits as a
+ * context that never calls this).  The Adam step size of a network follows its own lr and its own iteration
+ * count; when either differs between networks the episode uploads a [T][n_nets] step-size table.  The shared
+ * network's reduce / Adam kernels (and the act kernel's fused Adam step) and p2pmg_dqn_train_batch read row 0,
+ * or row `net`.  Both act kernels and the greedy evaluation (p2pmg_dqn_run_greedy) read the per-agent comfort
+ * weight; of a greedy episode only the recorded rewards depend on it.  A change takes effect at the next launch
+ * (a train episode or p2pmg_dqn_train_batch): a learning-rate or tau schedule across episodes needs no new
+ * context, and the Adam moments and iteration counts are not reset.  Over several ranks every rank of a shared
+ * network must be given the same row, as it must hold the same weights. */
+int p2pmg_dqn_set_learning(p2pmg_ctx* ctx, const double* gamma, const double* tau, const double* lr,
+                           const double* clip, const float* penalty_weight /* [A], per AGENT */);
+/* the values in use: gamma, tau, lr, clip [n_nets], penalty_weight [A]; any output may be NULL */
+int p2pmg_dqn_get_learning(p2pmg_ctx* ctx, double* gamma, double* tau, double* lr, double* clip,
+                           float* penalty_weight);
+/* One DQN episode with one exploration rate per scenario, eps [S] in [0, 1]: modes TRAIN and FILL with
+ * P2PMG_RNG_PHILOX only (replay codes already carry each agent's decision: REPLAY and GREEDY return
+ * P2PMG_E_INVALID).  args->epsilon is not read.  Each scenario's {threshold, explore-all} pair is formed exactly
+ * as p2pmg_run_episodes_eps forms it and read by both act kernels (the MFMA act kernel per agent slot: a
+ * workgroup's slots may span scenarios), so scenario s explores as a p2pmg_run_episode at epsilon = eps[s]
+ * would, bit for bit. */
+int p2pmg_dqn_run_episode_eps(p2pmg_ctx* ctx, const p2pmg_episode_args* args, const double* eps /* [S] */);
 
 /* The DQN policy map: what the table digests are for a Q-table, for a Q-network.  For each network the
  * Q-MLP is evaluated ON THE DEVICE at every state of a rectangular grid of observations and at the three

@@ -31,6 +31,7 @@ POLICY_UNVISITED = 255   # P2PMG_POLICY_UNVISITED
 SPARSE_STAGE_BYTES = 8 << 20  # P2PMG_SPARSE_STAGE_BYTES
 
 EXPORTS = [
+    "p2pmg_dqn_set_learning", "p2pmg_dqn_get_learning", "p2pmg_dqn_run_episode_eps",
     "p2pmg_abi_version", "p2pmg_config_default", "p2pmg_create", "p2pmg_destroy", "p2pmg_last_error", "p2pmg_last_kernel",
     "p2pmg_sync", "p2pmg_device_info", "p2pmg_set_env", "p2pmg_set_profiles", "p2pmg_set_agent_params",
     "p2pmg_set_temperatures", "p2pmg_get_temperatures", "p2pmg_reset_temperatures_philox",
@@ -193,6 +194,10 @@ def _declare(lib):
         "p2pmg_dqn_set_buffer": ([vp, i32, i32, vp, vp], i32),
         "p2pmg_dqn_forward": ([vp, i32, i32, vp, vp], i32),
         "p2pmg_dqn_train_batch": ([vp, i32, vp, vp], i32),
+        # gamma, tau, lr, clip [n_nets] f64, penalty_weight [A] f32; NULL = leave as is (all NULL: the setup's values)
+        "p2pmg_dqn_set_learning": ([vp, vp, vp, vp, vp, vp], i32),
+        "p2pmg_dqn_get_learning": ([vp, vp, vp, vp, vp, vp], i32),
+        "p2pmg_dqn_run_episode_eps": ([vp, C.POINTER(EpisodeArgs), dp], i32),  # eps [S] f64
         "p2pmg_dqn_set_grid": ([vp, vp, vp, vp, vp, vp], i32),      # n [4] i32, four f32 axes (all NULL: default)
         "p2pmg_dqn_get_grid": ([vp, vp, vp], i32),                  # n [4] i32, axes f32 or NULL
         "p2pmg_dqn_policy_map": ([vp, i32, i32, i32, vp, vp], i32),  # policy [count][G] u8, q [count][G][3] f32

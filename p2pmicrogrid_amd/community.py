@@ -60,6 +60,15 @@ def learning_arrays(agents) -> Tuple[np.ndarray, np.ndarray]:
     return alpha, gamma
 
 
+def dqn_learning_arrays(agents) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Each DQNAgent's own Trainer constants (agent.py:306-311, rl.py:253-266): (gamma [N], tau [N], lr [N])
+    f64, what DeviceDQNBatch.set_learning takes.  Pure NumPy."""
+    gamma = np.array([float(a.trainer._gamma) for a in agents], np.float64)
+    tau = np.array([float(a.trainer._tau) for a in agents], np.float64)
+    lr = np.array([float(a.trainer.optimizer.learning_rate) for a in agents], np.float64)
+    return gamma, tau, lr
+
+
 class CommunityMicrogrid:
 
     def __init__(self, timeline, agents: List[ActingAgent], rounds: int, q_dtype: Optional[str] = None,
@@ -165,6 +174,14 @@ class CommunityMicrogrid:
             learning_key = (alpha.tobytes(), gamma.tobytes())
             if self._uploaded.get("learning") != learning_key:
                 eng.set_learning(alpha=alpha[None], gamma=gamma[None])
+                self._uploaded["learning"] = learning_key
+        if self._dqn:
+            # every trainer's own gamma, tau and learning rate, keyed on the values in the same way: a change
+            # between episodes (agent.trainer._tau = ...) is uploaded again, the Adam state staying as it is
+            gamma, tau, lr = dqn_learning_arrays(self.agents)
+            learning_key = (gamma.tobytes(), tau.tobytes(), lr.tobytes())
+            if self._uploaded.get("learning") != learning_key:
+                eng.set_learning(gamma=gamma[None], tau=tau[None], lr=lr[None])
                 self._uploaded["learning"] = learning_key
         return eng
 

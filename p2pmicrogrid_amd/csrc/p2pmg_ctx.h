@@ -229,6 +229,14 @@ struct p2pmg_ctx : p2pmg::PlanFacts {
   std::vector<int32_t> h_pol_map;
   int pol_count = 0;            // 0: no set
   std::vector<int64_t> d_steps;  // Adam iterations done, per network (agent.py:310: one optimizer per agent)
+  // p2pmg_dqn_set_learning: each network's {gamma, tau, lr, clip} and each agent's comfort weight, their
+  // device forms ([n_nets] {gamma, tau, 1 - tau, clip} as f32, [A] f32), and whether two rows differ in
+  // what the train kernel reads (d_hyp_mixed: it then loads its row) or in lr (d_lr_mixed: the lr table)
+  std::vector<p2pmg::DqnLearn> h_dlearn;
+  std::vector<float> h_penw;
+  DevBuf<float4> d_hyp;
+  DevBuf<float> d_penw;
+  bool d_hyp_mixed = false, d_lr_mixed = false;
   DevBuf<float> d_lr;      // [T][n_nets] per-network step sizes of one episode when the counts differ
   std::vector<float> h_lr;
   int64_t d_added_min = 0;    // every ring holds at least this many transitions

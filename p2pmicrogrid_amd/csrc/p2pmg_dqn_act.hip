@@ -97,6 +97,7 @@ __global__ __launch_bounds__((dqn_act_waves<NC, WIDE>() * kWave)) void dqn_act_k
   const float time_t = e0[0], t_out = e0[1], buy = e0[2], inj = e0[3], p2pp = e0[4];
   const float time_n = e1[0];
   const bool greedy_mode = p.mode == 1;
+  const uint2 eps_s = dqn_eps_of(p, s);  // the scenario's exploration thresholds (workgroup-uniform)
   // the wave's agents: wave-uniform scalars (registers for one agent per wave, LDS for several) and
   // this lane's hidden unit of the agent's network (rl.py:139-141): first-layer column, biases,
   // output weight (registers for one agent per wave, read where used for several: L2 hits)
@@ -105,6 +106,7 @@ __global__ __launch_bounds__((dqn_act_waves<NC, WIDE>() * kWave)) void dqn_act_k
     float mi, tin, tm, bal, baln, tnorm;
     float4 lv;
     float4 th;  // the agent's {setpoint, lower, upper, cop} (EpisodeParams::thermal)
+    float penw;  // its comfort weight (DqnParams::penw)
     int act;
     float hp, p2pf;
   };
@@ -138,6 +140,7 @@ __global__ __launch_bounds__((dqn_act_waves<NC, WIDE>() * kWave)) void dqn_act_k
     g.bal = (f0.x - f0.y) / g.mi;  // RLAgent._get_balance agent.py:172-176
     g.baln = (f1.x - f1.y) / g.mi;
     g.th = p.thermal[g.a];
+    g.penw = d.penw[g.a];
     g.tnorm = (g.tin - g.th.x) / p.margin;  // HPHeating.normalized_temperature heating.py:118-120
     g.lv = p.hp_lv[g.a];
     g.act = 0;
@@ -167,8 +170,8 @@ __global__ __launch_bounds__((dqn_act_waves<NC, WIDE>() * kWave)) void dqn_act_k
           code = replay_code(p, t, W, A, r, a);
         } else {
           // word k = t (R + 1) + r of the agent's decision stream (p2pmg_device.h, oracle/philox.py::decision_draws)
-          code = (int)philox_round_code(t, R1, r, (uint32_t)p.episode, p.agent_offset + (uint32_t)a, p.eps_thr,
-                                        p.eps_all, p.seed_lo, p.seed_hi);
+          code = (int)philox_round_code(t, R1, r, (uint32_t)p.episode, p.agent_offset + (uint32_t)a, eps_s.x,
+                                        (int)eps_s.y, p.seed_lo, p.seed_hi);
         }
       }
       if (code == 255) {
@@ -240,7 +243,7 @@ __global__ __launch_bounds__((dqn_act_waves<NC, WIDE>() * kWave)) void dqn_act_k
       gg = gg + (pij - ex);
       pp = pp + ex;
     }
-    const Settled st = settle(p, gg, pp, buy, inj, p2pp, g.tin, g.th);
+    const Settled st = settle(p, gg, pp, buy, inj, p2pp, g.tin, g.th, g.penw);
     const float cost = st.cost, rw = st.rw;
 
     if (p.mode != 1) {

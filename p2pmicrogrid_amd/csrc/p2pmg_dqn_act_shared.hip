@@ -55,6 +55,9 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
   const int c16 = l & 15, g4 = l >> 4;
   const int t = d.t, T = p.T, tn = (t + 1 == T) ? 0 : t + 1;
   const int R1 = p.R + 1, W = (R1 + 3) >> 2;
+  // act_shared_mfma, the launch's gate: every round's code fits codes_pack, so the per-scenario thresholds
+  // are dead after the prologue (no per-lane pair held across the rounds)
+  __builtin_assume(R1 <= 8);
   const size_t A = (size_t)p.A;
   const bool greedy_mode = p.mode == 1;
   const int s0 = blockIdx.x * SPW;
@@ -74,6 +77,7 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
         tnorm = 0.0f;
   float4 lv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float4 tp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the agent's {setpoint, lower, upper, cop}
+  float penw = 0.0f;                                // its comfort weight (DqnParams::penw)
   if (agent_thr) {
     time_t = e0[0];
     t_out = e0[1];
@@ -88,6 +92,7 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
     bal = (f0.x - f0.y) / mi;  // RLAgent._get_balance agent.py:172-176
     baln = (f1.x - f1.y) / mi;
     tp = p.thermal[a];
+    penw = d.penw[a];
     tnorm = (tin - tp.x) / p.margin;  // HPHeating.normalized_temperature heating.py:118-120
     lv = p.hp_lv[a];
   }
@@ -121,6 +126,8 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
   // every round's exploration draw (or replayed code) ahead of the rounds: they depend only on
   // (t, episode, agent), so they run under the prologue's load latency, off the rounds' chain
   uint64_t codes_pack = ~0ull;  // byte r: code of round r < 8 (255 = greedy); later rounds are drawn in the loop
+  // the agent's scenario's exploration thresholds: a workgroup's agent slots may span scenarios
+  uint2 eps_s = make_uint2(p.eps_thr, (uint32_t)p.eps_all);
   if (agent_thr && !greedy_mode) {
     if (p.rng == 0) {
       for (int w4 = 0; w4 < W && w4 < 2; ++w4)
@@ -128,7 +135,8 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
                      ((uint64_t)replay_word(p, t, W, A, w4, a) << (32 * w4));
     } else {
       // every round's code of step t (p2pmg_device.h, oracle/philox.py::decision_draws)
-      codes_pack = philox_step_codes(t, R1, (uint32_t)p.episode, p.agent_offset + (uint32_t)a, p.eps_thr, p.eps_all,
+      eps_s = dqn_eps_of(p, s);
+      codes_pack = philox_step_codes(t, R1, (uint32_t)p.episode, p.agent_offset + (uint32_t)a, eps_s.x, (int)eps_s.y,
                                      p.seed_lo, p.seed_hi);
     }
   }
@@ -157,8 +165,8 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
         if (r < 8) code = (int)((codes_pack >> (8 * r)) & 0xFFu);
         else if (p.rng == 0) code = replay_code(p, t, W, A, r, a);
         else
-          code = (int)philox_round_code(t, R1, r, (uint32_t)p.episode, p.agent_offset + (uint32_t)a, p.eps_thr,
-                                        p.eps_all, p.seed_lo, p.seed_hi);
+          code = (int)philox_round_code(t, R1, r, (uint32_t)p.episode, p.agent_offset + (uint32_t)a, eps_s.x,
+                                        (int)eps_s.y, p.seed_lo, p.seed_hi);
       }
       greedy = code == 255;
       shX[j] = make_float4(time_t, tnorm, bal, p2pf);
@@ -254,7 +262,7 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
       g = g + (pij - ex);
       pp = pp + ex;
     }
-    const Settled st = settle(p, g, pp, buy, inj, p2pp, tin, tp);
+    const Settled st = settle(p, g, pp, buy, inj, p2pp, tin, tp, penw);
     cost = st.cost;
     rw = st.rw;
     // HPHeating.step heating.py:138-143 at the agent's COP

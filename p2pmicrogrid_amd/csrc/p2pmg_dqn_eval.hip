@@ -59,6 +59,7 @@ __global__ __launch_bounds__((dqn_eval_waves<NC, WIDE>() * kWave)) void dqn_gree
     float mi, tin, tm, bal, tnorm;
     float4 lv;
     float4 th;  // the agent's {setpoint, lower, upper, cop} (EpisodeParams::thermal)
+    float penw;  // its comfort weight (DqnEvalParams::penw): only the recorded rewards depend on it
     int act;
     float hp, p2pf;
     float2 fnext;      // the agent's profile row of the next step
@@ -91,6 +92,7 @@ __global__ __launch_bounds__((dqn_eval_waves<NC, WIDE>() * kWave)) void dqn_gree
     g.tin = p.t_in[g.a];
     g.tm = p.t_m[g.a];
     g.th = p.thermal[g.a];
+    g.penw = d.penw[g.a];
     g.lv = p.hp_lv[g.a];
     g.act = 0;
     g.hp = 0.0f;
@@ -212,7 +214,7 @@ __global__ __launch_bounds__((dqn_eval_waves<NC, WIDE>() * kWave)) void dqn_gree
         gg = gg + (pij - ex);
         pp = pp + ex;
       }
-      const Settled st = settle(p, gg, pp, buy, inj, p2pp, g.tin, g.th);
+      const Settled st = settle(p, gg, pp, buy, inj, p2pp, g.tin, g.th, g.penw);
       if (lane == 0) {
         const size_t kr = (size_t)t * A + a;
         if (p.record & 1) p.rec_reward[kr] = st.rw;

@@ -35,19 +35,20 @@ __device__ __forceinline__ int replay_code(const EpisodeParams& p, int t, int W,
 }
 
 // _compute_costs community.py:56-65; RLAgent.get_reward agent.py:225-232 (pre-update T_in) from the
-// agent's grid and p2p power and its thermal {setpoint, lower, upper, cop}
+// agent's grid and p2p power, its thermal {setpoint, lower, upper, cop} and its own comfort weight penw
+// (DqnParams::penw / DqnEvalParams::penw, p2pmg_dqn_set_learning)
 struct Settled {
   float cost, rw;
 };
 __device__ __forceinline__ Settled settle(const EpisodeParams& p, float gg, float pp, float buy, float inj, float p2pp,
-                                          float tin, float4 thermal) {
+                                          float tin, float4 thermal, float penw) {
   float cost = (gg >= 0.0f) ? gg * buy : gg * inj;
   cost = cost + pp * p2pp;
   cost = (cost * p.slot) / p.mph;
   cost = cost * p.kilo;
   float pen = fmaxf(fmaxf(0.0f, thermal.y - tin), fmaxf(0.0f, tin - thermal.z));
   pen = pen > 0.0f ? pen + 1.0f : 0.0f;
-  return Settled{cost, -(cost + p.penw * pen)};
+  return Settled{cost, -(cost + penw * pen)};
 }
 
 // Keras Adam (beta1 .9, beta2 .999, eps 1e-7; rl.py:335-354) on one parameter, Trainer._soft_update, and
@@ -61,7 +62,13 @@ __device__ __forceinline__ AdamStep adam_step(const DqnParams& d, float m, float
   w = w - (m * lr) / (sqrtf(v) + d.adam_eps);
   return AdamStep{m, v, w};
 }
-__device__ __forceinline__ float soft_update(const DqnParams& d, float tg, float w) { return d.tau_c * tg + d.tau * w; }
+__device__ __forceinline__ float soft_update(float tau, float tau_c, float tg, float w) { return tau_c * tg + tau * w; }
+__device__ __forceinline__ float soft_update(const DqnParams& d, float tg, float w) { return soft_update(d.tau, d.tau_c, tg, w); }
+// the exploration thresholds of scenario s: the launch's scalars, or the scenario's own pair of the
+// per-scenario table (p2pmg_dqn_run_episode_eps), {thr, all} as eps_threshold forms them
+__device__ __forceinline__ uint2 dqn_eps_of(const EpisodeParams& p, int s) {
+  return p.eps_tab ? p.eps_tab[s] : make_uint2(p.eps_thr, (uint32_t)p.eps_all);
+}
 __device__ __forceinline__ float shared_grad(const DqnParams& d, int k, float t) {
   float gk = t * d.inv_agents;
   if (k < kOffB1) gk = fminf(fmaxf(gk, -d.clip), d.clip);

@@ -19,14 +19,15 @@ namespace {
 constexpr int kLdsRowT = 48;  // H1oT rows (32 data rows + pad): 16 units x 4 k of one read hit 64 banks
 
 // ----------------------------------------------------------------- train: Trainer._train
-__device__ __forceinline__ void adam_update(const DqnParams& d, float* th, float* tg, float* mm, float* vv, int idx,
-                                            float g, float lr) {
+// hyp: the network's own {gamma, tau, tau_c, clip} (wave-uniform)
+__device__ __forceinline__ void adam_update(const DqnParams& d, float4 hyp, float* th, float* tg, float* mm, float* vv,
+                                            int idx, float g, float lr) {
   // Keras Adam then Trainer._soft_update (rl.py:335-354), in place
   const AdamStep s = adam_step(d, mm[idx], vv[idx], th[idx], g, lr);
   mm[idx] = s.m;
   vv[idx] = s.v;
   th[idx] = s.w;
-  tg[idx] = soft_update(d, tg[idx], s.w);
+  tg[idx] = soft_update(hyp.y, hyp.z, tg[idx], s.w);
 }
 
 // one thread's share of agent a's sampled batch (thread t: sample t / 8, floats t % 8 and, for
@@ -113,6 +114,11 @@ __global__ __launch_bounds__(256, P2PMG_TRAIN_OCC) void dqn_train_kernel(const D
   const int a_first = seg * d.seg_agents + sblk * d.apb;
   const int n_ag = d.batch ? 1 : max(0, min(d.apb, (seg + 1) * d.seg_agents - a_first));
   int net = d.batch ? d.net : 0;
+  // the workgroup's network's {gamma, tau, tau_c, clip}: per-agent networks train one agent per workgroup,
+  // so its row (d.hyp, when the networks' constants differ) is one scalar load from a uniform address,
+  // and the four values stay SGPRs like the kernel arguments they stand in for
+  const int net_h = __builtin_amdgcn_readfirstlane(d.batch ? d.net : (SHARED ? 0 : a_first));
+  const float4 hyp = d.hyp ? d.hyp[net_h] : make_float4(d.gamma, d.tau, d.tau_c, d.clip);
   TrainW W;
   // one shared network: the lane's 48 W2 operands (layer 2: W2[4 kk + g4][col] of the target and
   // the online network; dH1: W2[col][4 kk + g4]) stay in registers for the whole launch
@@ -272,7 +278,7 @@ __global__ __launch_bounds__(256, P2PMG_TRAIN_OCC) void dqn_train_kernel(const D
       }
       const int ro = 3 * kB + b;
       const float q = (((qpart[0][ro] + qpart[1][ro]) + qpart[2][ro]) + qpart[3][ro]) + W.b3o;
-      const float y = smp[b][5] + d.gamma * fmaxf(fmaxf(qt[0], qt[1]), qt[2]);
+      const float y = smp[b][5] + hyp.x * fmaxf(fmaxf(qt[0], qt[1]), qt[2]);
       const float diff = q - y;
       dq[rt] = (2.0f / (float)kB) * diff;
       lsum += diff * diff;
@@ -405,21 +411,21 @@ __global__ __launch_bounds__(256, P2PMG_TRAIN_OCC) void dqn_train_kernel(const D
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) adam_update(d, th, tg, mm, vv, kOffW2 + (16 * mt + 4 * g4 + r) * kH + col, gW2[mt][r], lr);
+      for (int r = 0; r < 4; ++r) adam_update(d, hyp, th, tg, mm, vv, kOffW2 + (16 * mt + 4 * g4 + r) * kH + col, gW2[mt][r], lr);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int k = 4 * g4 + r;
-      if (k < 5) adam_update(d, th, tg, mm, vv, kOffW1 + k * kH + col, fminf(fmaxf(dw1(r), -d.clip), d.clip), lr);
+      if (k < 5) adam_update(d, hyp, th, tg, mm, vv, kOffW1 + k * kH + col, fminf(fmaxf(dw1(r), -hyp.w), hyp.w), lr);
     }
-    if (g4 == 0) adam_update(d, th, tg, mm, vv, kOffB1 + col, gb1, lr);
+    if (g4 == 0) adam_update(d, hyp, th, tg, mm, vv, kOffB1 + col, gb1, lr);
     if (c16 == 0) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        adam_update(d, th, tg, mm, vv, kOffB2 + h0 + r, gb2[r], lr);
-        adam_update(d, th, tg, mm, vv, kOffW3 + h0 + r, gW3[r], lr);
+        adam_update(d, hyp, th, tg, mm, vv, kOffB2 + h0 + r, gb2[r], lr);
+        adam_update(d, hyp, th, tg, mm, vv, kOffW3 + h0 + r, gW3[r], lr);
       }
     }
-    if (threadIdx.x == 0) adam_update(d, th, tg, mm, vv, kOffB3, gb3, lr);
+    if (threadIdx.x == 0) adam_update(d, hyp, th, tg, mm, vv, kOffB3, gb3, lr);
   } else {
     float* gp = d.grad + (size_t)blockIdx.x * kNetStride;
 #pragma unroll

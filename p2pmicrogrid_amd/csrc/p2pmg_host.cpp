@@ -3,6 +3,7 @@
 // alone into a program that runs under sanitizers.
 #include "p2pmg_host.h"
 
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 
@@ -22,6 +23,24 @@ int validate_config(const p2pmg_config* cfg, std::string* why) {
     if (why) *why = "create: shared_q = P2PMG_SHARED_ROLE needs learner = TABULAR (a Q-network per role is not built)";
     return P2PMG_E_UNSUPPORTED;
   }
+  return P2PMG_OK;
+}
+
+int validate_dqn_learning(const DqnLearn* rows, int n_nets, const float* penw, int n_agents, std::string* why) {
+  if (why) why->clear();
+  auto bad = [&](const char* what, const char* unit, int k) {
+    if (why) *why = std::string("dqn_set_learning: ") + what + " for " + unit + " " + std::to_string(k);
+    return P2PMG_E_INVALID;
+  };
+  for (int k = 0; k < n_nets; ++k) {
+    const DqnLearn& r = rows[k];
+    if (!(std::isfinite(r.gamma) && r.gamma >= 0.0 && r.gamma <= 1.0)) return bad("gamma outside [0, 1]", "network", k);
+    if (!(std::isfinite(r.tau) && r.tau >= 0.0 && r.tau <= 1.0)) return bad("tau outside [0, 1]", "network", k);
+    if (!(std::isfinite(r.lr) && r.lr >= 0.0)) return bad("negative or non-finite lr", "network", k);
+    if (!(std::isfinite(r.clip) && r.clip > 0.0)) return bad("clip not positive and finite", "network", k);
+  }
+  for (int a = 0; a < n_agents; ++a)
+    if (!(std::isfinite(penw[a]) && penw[a] >= 0.0f)) return bad("negative or non-finite penalty weight", "agent", a);
   return P2PMG_OK;
 }
 

@@ -17,4 +17,13 @@ constexpr int kMaxRounds1 = 4096;
 // *why (cleared first) the message p2pmg_last_error(NULL) then gives, where there is one.  Not exported.
 __attribute__((visibility("hidden"))) int validate_config(const p2pmg_config* cfg, std::string* why);
 
+// One network's learner constants as p2pmg_dqn_set_learning takes them
+struct DqnLearn {
+  double gamma, tau, lr, clip;
+};
+// What p2pmg_dqn_set_learning checks before it uploads: P2PMG_OK, or P2PMG_E_INVALID with *why naming the first
+// offending network (rows [n_nets]) or agent (penw [n_agents]).  Not exported.
+__attribute__((visibility("hidden"))) int validate_dqn_learning(const DqnLearn* rows, int n_nets, const float* penw,
+                                                                int n_agents, std::string* why);
+
 }  // namespace p2pmg

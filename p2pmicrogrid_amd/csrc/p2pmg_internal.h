@@ -133,7 +133,13 @@ struct DqnParams {
   int act_agw;               // shared network, MFMA act kernel: agent slots per workgroup (16, or 8 for N <= 8)
   float* rec_loss;           // [T][A] or null
   float* ep_acc;             // [S] running sum_t mean_i r
+  // the learner constants of every network when they are equal (always so for one shared network), as f32
+  // casts of p2pmg_dqn_config / p2pmg_dqn_set_learning's doubles; tau_c = 1 - tau
   float gamma, tau, tau_c, lr_t, b1c, b2c, adam_eps, clip;
+  // per-agent networks whose constants differ: [n_nets] rows {gamma, tau, tau_c, clip}, one 16-B scalar
+  // load per train workgroup (its network is uniform); else null: the scalars above
+  const float4* hyp;
+  const float* penw;         // [A] per-agent comfort weight of the reward (p2pmg_dqn_set_learning)
   const float* lr_net;       // per-agent networks whose Adam step counts differ: [n_nets] step sizes (else null: lr_t)
   float inv_agents;          // shared: 1 / (agents over all ranks)
   int apb;                   // agents per train workgroup
@@ -175,6 +181,7 @@ struct DqnEvalParams {
   const float* nets;         // [count][kNetStride] the networks the episode reads
   const int32_t* net_of;     // [A] agent -> network of `nets`; null: the context's own arrays (one_net)
   int one_net;               // net_of == null: 1 = every agent reads network 0, 0 = agent a reads network a
+  const float* penw;         // [A] per-agent comfort weight of the recorded rewards (as DqnParams::penw)
   float* ep_acc;             // [S] left as the stepwise episode leaves it (= ep_reward)
 };
 // dqn_greedy_episode_kernel<N>: one workgroup per scenario, any N in 1..kMaxAgents

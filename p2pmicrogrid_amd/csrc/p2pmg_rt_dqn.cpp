@@ -64,13 +64,17 @@ p2pmg::DqnParams dqn_params(p2pmg_ctx* c, const EpisodeParams& e) {
   d.samples = nullptr;
   d.rec_loss = (e.record & P2PMG_REC_LOSS) ? c->rec_loss : nullptr;
   d.ep_acc = c->d_ep_acc;
-  d.gamma = (float)q.gamma;
-  d.tau = (float)q.tau;
-  d.tau_c = 1.0f - (float)q.tau;
+  // row 0: every row when they are equal, and what the shared network's kernels read
+  const p2pmg::DqnLearn& r0 = c->h_dlearn[0];
+  d.gamma = (float)r0.gamma;
+  d.tau = (float)r0.tau;
+  d.tau_c = 1.0f - (float)r0.tau;
   d.b1c = 1.0f - (float)q.beta1;
   d.b2c = 1.0f - (float)q.beta2;
   d.adam_eps = (float)q.adam_eps;
-  d.clip = (float)q.clip;
+  d.clip = (float)r0.clip;
+  d.hyp = c->d_hyp_mixed ? c->d_hyp.get() : nullptr;
+  d.penw = c->d_penw;
   d.inv_agents = 1.0f / (float)((double)c->A * c->nranks);
   d.apb = c->d_apb;
   d.theta_out = d.theta;  // the Adam steps store in place unless the episode loop binds the double buffer
@@ -96,18 +100,34 @@ void dqn_bind(p2pmg::DqnParams& d, float* const in[4], float* const out[4]) {
 }
 
 // Keras Adam step size for iteration `step` (1-based), float64 -> float32 (oracle/dqn.py::adam_lr)
-float adam_lr(const p2pmg_dqn_config& q, int64_t step) {
+// at the network's own learning rate lr
+float adam_lr(const p2pmg_dqn_config& q, double lr, int64_t step) {
   const double t = (double)step;
-  return (float)(q.lr * std::sqrt(1.0 - std::pow(q.beta2, t)) / (1.0 - std::pow(q.beta1, t)));
+  return (float)(lr * std::sqrt(1.0 - std::pow(q.beta2, t)) / (1.0 - std::pow(q.beta1, t)));
 }
 
+// every network takes the same Adam step size: the iteration counts the same and lr the same
 bool dqn_steps_same(const p2pmg_ctx* c) {
   for (int64_t st : c->d_steps)
     if (st != c->d_steps[0]) return false;
-  return true;
+  return !c->d_lr_mixed;
 }
 
-// p2pmg_dqn_train_batch advanced some networks on their own, so their Adam step counts differ.
+// h_dlearn / h_penw to the device, and what the rows have in common
+int dqn_upload_learning(p2pmg_ctx* c) {
+  std::vector<float4> hyp(c->h_dlearn.size());
+  c->d_hyp_mixed = c->d_lr_mixed = false;
+  for (size_t k = 0; k < hyp.size(); ++k) {
+    const p2pmg::DqnLearn& r = c->h_dlearn[k];
+    hyp[k] = make_float4((float)r.gamma, (float)r.tau, 1.0f - (float)r.tau, (float)r.clip);
+    if (std::memcmp(&hyp[k], &hyp[0], sizeof(float4)) != 0) c->d_hyp_mixed = true;
+    if (r.lr != c->h_dlearn[0].lr) c->d_lr_mixed = true;
+  }
+  return upload(c, {{c->d_hyp, hyp.data(), hyp.size() * sizeof(float4)}, {c->d_penw, c->h_penw.data(), c->h_penw.size() * 4}});
+}
+
+// p2pmg_dqn_train_batch advanced some networks on their own, so their Adam step counts differ, or
+// p2pmg_dqn_set_learning gave them different learning rates.
 // Every env step advances every network by one, so an episode's per-network step sizes are known
 // up front: one [T][n_nets] table, uploaded once per episode (not a copy + sync per env step).
 int dqn_upload_lr_table(p2pmg_ctx* c) {
@@ -115,7 +135,7 @@ int dqn_upload_lr_table(p2pmg_ctx* c) {
   HIP_TRY(c, c->d_lr.grow(need));
   c->h_lr.resize(need);
   for (int t = 0; t < c->T; ++t)
-    for (size_t k = 0; k < n; ++k) c->h_lr[(size_t)t * n + k] = adam_lr(c->dcfg, c->d_steps[k] + 1 + t);
+    for (size_t k = 0; k < n; ++k) c->h_lr[(size_t)t * n + k] = adam_lr(c->dcfg, c->h_dlearn[k].lr, c->d_steps[k] + 1 + t);
   return upload(c, {{c->d_lr, c->h_lr.data(), need * 4}});  // synced: h_lr is rewritten by the next such episode
 }
 
@@ -159,7 +179,7 @@ int dqn_train_step(p2pmg_ctx* c, p2pmg::DqnParams& d, bool same, bool defer) {
   // one env step trains every network once (community.py:158-168); the Adam step counters advance
   // only once every launch of the step is enqueued (a failed exchange leaves weights and counters
   // at the previous step: the Adam launch that would change the weights was not issued)
-  d.lr_t = adam_lr(c->dcfg, c->d_steps[0] + 1);
+  d.lr_t = adam_lr(c->dcfg, c->h_dlearn[0].lr, c->d_steps[0] + 1);
   d.lr_net = same ? nullptr : c->d_lr + (size_t)d.t * c->d_steps.size();
   if (!d.fused_sample) HIP_TRY(c, p2pmg::launch_dqn_sample(d, c->stream));
   if (c->n_nets == 1) {
@@ -340,7 +360,85 @@ int p2pmg_dqn_setup(p2pmg_ctx* c, const p2pmg_dqn_config* cfg) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->d_steps.assign((size_t)c->n_nets, 0);
   c->d_added_min = 0;
+  HIP_TRY(c, c->d_hyp.alloc((size_t)c->n_nets));
+  HIP_TRY(c, c->d_penw.alloc(A));
+  c->h_dlearn.assign((size_t)c->n_nets, p2pmg::DqnLearn{cfg->gamma, cfg->tau, cfg->lr, cfg->clip});
+  c->h_penw.assign(A, c->cfg.penalty_weight);
+  return dqn_upload_learning(c);
+}
+
+int p2pmg_dqn_set_learning(p2pmg_ctx* c, const double* gamma, const double* tau, const double* lr, const double* clip,
+                           const float* penalty_weight) {
+  if (!c) return P2PMG_E_INVALID;
+  if (!c->dqn || !c->d_theta) return fail(c, P2PMG_E_STATE, "dqn_set_learning: a DQN context after p2pmg_dqn_setup");
+  const bool restore = !gamma && !tau && !lr && !clip && !penalty_weight;
+  const p2pmg_dqn_config& q = c->dcfg;
+  std::vector<p2pmg::DqnLearn> rows = c->h_dlearn;
+  std::vector<float> penw = c->h_penw;
+  if (restore) {
+    rows.assign(rows.size(), p2pmg::DqnLearn{q.gamma, q.tau, q.lr, q.clip});
+    penw.assign(penw.size(), c->cfg.penalty_weight);
+  }
+  for (size_t k = 0; k < rows.size(); ++k) {
+    if (gamma) rows[k].gamma = gamma[k];
+    if (tau) rows[k].tau = tau[k];
+    if (lr) rows[k].lr = lr[k];
+    if (clip) rows[k].clip = clip[k];
+  }
+  if (penalty_weight) std::copy(penalty_weight, penalty_weight + penw.size(), penw.begin());
+  std::string why;  // validated in full before anything changes
+  if (!restore && p2pmg::validate_dqn_learning(rows.data(), (int)rows.size(), penw.data(), (int)penw.size(), &why) != P2PMG_OK)
+    return fail(c, P2PMG_E_INVALID, why);
+  std::swap(c->h_dlearn, rows);
+  std::swap(c->h_penw, penw);
+  const int rc = dqn_upload_learning(c);
+  if (rc != P2PMG_OK) {  // the upload failed: the host copies go back too
+    std::swap(c->h_dlearn, rows);
+    std::swap(c->h_penw, penw);
+    (void)dqn_upload_learning(c);
+  }
+  return rc;
+}
+
+int p2pmg_dqn_get_learning(p2pmg_ctx* c, double* gamma, double* tau, double* lr, double* clip, float* penalty_weight) {
+  if (!c) return P2PMG_E_INVALID;
+  if (!c->dqn || !c->d_theta) return fail(c, P2PMG_E_STATE, "dqn_get_learning: a DQN context after p2pmg_dqn_setup");
+  for (size_t k = 0; k < c->h_dlearn.size(); ++k) {
+    if (gamma) gamma[k] = c->h_dlearn[k].gamma;
+    if (tau) tau[k] = c->h_dlearn[k].tau;
+    if (lr) lr[k] = c->h_dlearn[k].lr;
+    if (clip) clip[k] = c->h_dlearn[k].clip;
+  }
+  if (penalty_weight) std::copy(c->h_penw.begin(), c->h_penw.end(), penalty_weight);
   return P2PMG_OK;
+}
+
+int p2pmg_dqn_run_episode_eps(p2pmg_ctx* c, const p2pmg_episode_args* args, const double* eps) {
+  if (!c || !args || !eps) return P2PMG_E_INVALID;
+  if (!c->dqn || !c->d_theta) return fail(c, P2PMG_E_STATE, "dqn_run_episode_eps: a DQN context after p2pmg_dqn_setup");
+  if ((args->mode != P2PMG_MODE_TRAIN && args->mode != P2PMG_MODE_FILL) || args->rng != P2PMG_RNG_PHILOX)
+    return fail(c, P2PMG_E_INVALID, "dqn_run_episode_eps: Philox train or fill episodes only (replay codes carry each "
+                                    "agent's own decision, a greedy episode draws none)");
+  const size_t S = (size_t)c->S;
+  std::vector<uint2> tab(S);
+  for (size_t s = 0; s < S; ++s) {
+    if (!(std::isfinite(eps[s]) && eps[s] >= 0.0 && eps[s] <= 1.0))
+      return fail(c, P2PMG_E_INVALID, "dqn_run_episode_eps: epsilon outside [0, 1] for scenario " + std::to_string(s));
+    int all = 0;
+    p2pmg::eps_threshold(eps[s], tab[s].x, all);
+    tab[s].y = (uint32_t)all;
+  }
+  HIP_TRY(c, c->eps_tab.grow(S));
+  RC_TRY(upload(c, {{c->eps_tab, tab.data(), S * sizeof(uint2)}}));
+  c->chain_n = 0;
+  c->eps_table = true;  // episode_params binds the row (EpisodeParams::eps_tab)
+  c->eps_cur = c->eps_tab;
+  p2pmg_episode_args a = *args;
+  a.epsilon = eps[0];
+  const int rc = dqn_run_episode(c, &a);
+  c->eps_table = false;
+  c->eps_cur = nullptr;
+  return rc;
 }
 
 int p2pmg_dqn_set_weights(p2pmg_ctx* c, int which, int first, int count, const float* host) {
@@ -447,7 +545,7 @@ int p2pmg_dqn_train_batch(p2pmg_ctx* c, int net, const float* batch, float* loss
   d.batch = db;
   d.net = net;
   d.loss_out = db + p2pmg::kDqnBatch * p2pmg::kTrans;
-  d.lr_t = adam_lr(c->dcfg, ++c->d_steps[(size_t)net]);  // only this network's Adam iterates
+  d.lr_t = adam_lr(c->dcfg, c->h_dlearn[(size_t)net].lr, ++c->d_steps[(size_t)net]);  // only this network's Adam iterates
   hipError_t e = hipMemcpyAsync(db, batch, (size_t)p2pmg::kDqnBatch * p2pmg::kTrans * 4, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = p2pmg::launch_dqn_train(d, 1, false, c->stream);
   float l = 0.0f;

@@ -94,6 +94,7 @@ int p2pmg_dqn_run_greedy(p2pmg_ctx* c, int source, int record) {
     d.one_net = c->n_nets == 1 ? 1 : 0;
   }
   d.ep_acc = c->d_ep_acc;
+  d.penw = c->d_penw;
   Timed tm;
   RC_TRY(begin_timed(c, false, true, &tm));
   const hipError_t e = p2pmg::launch_dqn_greedy_episode(d, c->stream);

@@ -222,6 +222,35 @@ class ShardedTrainer:
             self.eng.set_q_delta(all_reduce_int64(self.eng.get_q_delta(), self.world))
         self.eng.apply_q_delta()
 
+    def _shard_rows(self, x):
+        """This shard's scenarios of a value that broadcasts to [S_total, N] (or [S_total] with ndim 1)."""
+        if x is None:
+            return None
+        x = np.asarray(x)
+        lo, hi = self.sh.first, self.sh.first + self.sh.count
+        return np.broadcast_to(x, (self.S_total, self.N))[lo:hi]
+
+    def set_learning(self, gamma=None, tau=None, lr=None, clip=None, penalty_weight=None):
+        """DQN learner: DeviceDQNBatch.set_learning on this rank's shard.  The shared network's row (gamma,
+        tau, lr, clip) goes through unchanged: every rank must be given the same one.  Per-agent values
+        (penalty_weight [S_total, N]; the four constants too when the shard's engine holds per-agent
+        networks) are sliced by the shard's scenario range."""
+        if self.learner != "dqn":
+            raise ValueError("ShardedTrainer.set_learning is the DQN learner's (tabular: eng.set_learning)")
+        rows = (gamma, tau, lr, clip)
+        if not getattr(self.eng, "shared", True):
+            rows = tuple(self._shard_rows(x) for x in rows)
+        self.eng.set_learning(*rows, penalty_weight=self._shard_rows(penalty_weight))
+
+    def _shard_eps(self, epsilon):
+        """A float as it is; an [S_total] vector of per-scenario rates cut to this shard's scenarios."""
+        if np.ndim(epsilon) == 0:
+            return float(epsilon)
+        eps = np.asarray(epsilon, np.float64)
+        if eps.shape != (self.S_total,):
+            raise ValueError(f"epsilon must be a float or [{self.S_total}], got {eps.shape}")
+        return np.ascontiguousarray(eps[self.sh.first:self.sh.first + self.sh.count])
+
     def fill_buffers(self, episodes: int = 1, reset_sigma: float = 0.3):
         """DQN: CommunityMicrogrid.init_buffers (community.py:125-147): episodes of acting at
         epsilon 1 that only store transitions (>= 31 per agent before training can start)."""
@@ -243,11 +272,12 @@ class ShardedTrainer:
         episode reward (sum_t mean_i r, community.py:179).  next_epsilon: the next episode's
         epsilon (the decay schedule, community.py:279-286), for the speculative pre-pass.
         DQN: the replay memory is filled first if it was not (fill_buffers); every env step's
-        gradient exchange happens inside the episode call."""
+        gradient exchange happens inside the episode call; epsilon may be an [S_total] vector of
+        per-scenario rates, of which each shard takes its scenarios."""
         if self.learner == "dqn":
             if not self.filled:
                 self.fill_buffers()
-            self.eng.run_episode("train", "philox", episode=self.episode, epsilon=epsilon)
+            self.eng.run_episode("train", "philox", episode=self.episode, epsilon=self._shard_eps(epsilon))
             total, count = self._metrics()
             self.eng.reset_temperatures_philox(self.episode + 1, reset_sigma)
             self.episode += 1
@@ -267,6 +297,8 @@ class ShardedTrainer:
         tables run as chained launches (p2pmg_run_episodes: the episodes back to back in every
         wave, results identical to train_episode per episode); a shared table or DQN network needs
         its exchange between episodes and runs train_episode per episode."""
+        if self.learner == "dqn" and np.ndim(epsilons) == 2:  # [n, S_total]: per-scenario rates
+            return np.array([self.train_episode(e, reset_sigma) for e in np.asarray(epsilons, np.float64)])
         eps = [float(e) for e in epsilons]
         if self.learner == "dqn" or self.shared_q:
             out = [self.train_episode(e, reset_sigma, eps[k + 1] if k + 1 < len(eps) else None)

@@ -18,7 +18,7 @@ W1[5][64] | b1[64] | W2[64][64] | b2[64] | W3[64][1] | b3[1].
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 
@@ -121,6 +121,40 @@ class DeviceDQNBatch(DeviceCommunityBatch):
         self._chk(self.L.p2pmg_dqn_get_net_steps(self._ctx, first, count, out.ctypes.data), "dqn_get_net_steps")
         return out
 
+    # ----------------------------------------------------------------- learner constants
+    def _net_shape(self):
+        return (1,) if self.shared else (self.S, self.N)
+
+    def set_learning(self, gamma=None, tau=None, lr=None, clip=None, penalty_weight=None):
+        """Per-network learner constants: each DQNAgent's own Trainer(gamma, tau, Adam(learning_rate))
+        (agent.py:306-311) and gradient clip, and each agent's comfort weight (agent.py:225-232).  gamma,
+        tau, lr and clip: scalars or anything that broadcasts to [S, N] (per-agent networks) or [1] (the
+        shared network); penalty_weight broadcasts to [S, N] in either case.  None leaves that field as it
+        is; set_learning() restores the values of the constructor.  Takes effect at the next launch; the
+        Adam moments and iteration counts stay (p2pmg_dqn_set_learning)."""
+        def cast(x, dt, shape):
+            if x is None:
+                return None
+            x = np.asarray(x, dt)
+            try:
+                return np.ascontiguousarray(np.broadcast_to(x, shape).reshape(-1))
+            except ValueError:
+                raise ValueError(f"learning arrays must broadcast to {list(shape)}, got {x.shape}") from None
+        rows = [cast(x, np.float64, self._net_shape()) for x in (gamma, tau, lr, clip)]
+        rows.append(cast(penalty_weight, F32, (self.S, self.N)))
+        self._chk(self.L.p2pmg_dqn_set_learning(self._ctx, *(None if x is None else x.ctypes.data for x in rows)),
+                  "dqn_set_learning")
+
+    def get_learning(self) -> Dict[str, np.ndarray]:
+        """{"gamma", "tau", "lr", "clip": f64 [S, N] (shared network: [1]), "penalty_weight": f32 [S, N]} in use."""
+        rows = [np.empty(self.n_nets, np.float64) for _ in range(4)]
+        w = np.empty(self.A, F32)
+        self._chk(self.L.p2pmg_dqn_get_learning(self._ctx, *(x.ctypes.data for x in rows), w.ctypes.data),
+                  "dqn_get_learning")
+        out = {k: x.reshape(self._net_shape()) for k, x in zip(("gamma", "tau", "lr", "clip"), rows)}
+        out["penalty_weight"] = w.reshape(self.S, self.N)
+        return out
+
     # ----------------------------------------------------------------- multi-rank shared network
     def grad_layout(self) -> dict:
         """Shared network: gradient segments of this context, agents per train workgroup, train
@@ -177,14 +211,26 @@ class DeviceDQNBatch(DeviceCommunityBatch):
     # ----------------------------------------------------------------- the hot path
     def run_episode(self, mode: str = "train", rng: str = "philox", episode: int = 0, epsilon: float = 1.0,
                     record: Sequence[str] = (), philox: str = "auto"):
-        """One episode of T steps for every scenario (asynchronous, stream-ordered)."""
+        """One episode of T steps for every scenario (asynchronous, stream-ordered).  epsilon: one rate, or
+        [S] rates, scenario s exploring at epsilon[s] as a launch at that scalar would (Philox train / fill
+        episodes only: p2pmg_dqn_run_episode_eps)."""
         mask = 0
         for r in record:
             mask |= _lib.REC[r]
+        eps = None
+        if np.ndim(epsilon) > 0:
+            eps = np.ascontiguousarray(epsilon, dtype=np.float64)
+            if eps.shape != (self.S,):
+                raise ValueError(f"epsilon must be a float or [{self.S}], got {eps.shape}")
+            if rng != "philox" or mode not in ("train", "fill"):
+                raise ValueError("per-scenario epsilon needs rng='philox' and mode 'train' or 'fill'")
         args = _lib.EpisodeArgs(MODES[mode], _lib.RNG_REPLAY if rng == "replay" else _lib.RNG_PHILOX,
-                                int(episode), mask, float(epsilon), 0, 0)
+                                int(episode), mask, float(epsilon if eps is None else eps[0]), 0, 0)
         self._xerr = None
-        st = self.L.p2pmg_run_episode(self._ctx, C.byref(args))
+        if eps is None:
+            st = self.L.p2pmg_run_episode(self._ctx, C.byref(args))
+        else:
+            st = self.L.p2pmg_dqn_run_episode_eps(self._ctx, C.byref(args), eps)
         if st != _lib.P2PMG_OK and self._xerr is not None:
             raise _lib.P2PMGError(f"run_episode: the gradient exchange raised {self._xerr!r}") from self._xerr
         self._chk(st, "run_episode")

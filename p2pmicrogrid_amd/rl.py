@@ -548,6 +548,16 @@ class Trainer:
         self.target_network.bind(engine, "target", slot)
         self.buffer.bind(engine, slot)
         self._engine, self._slot = engine, slot
+        # this trainer's own gamma, tau and Adam learning rate (rl.py:253-266) into its network's row of the
+        # engine's per-network arrays (a slot is a network where every agent has its own; a shared network
+        # keeps the engine's values)
+        if engine.n_nets == engine.A:
+            cur = engine.get_learning()
+            g, t, lr = (cur[k].reshape(-1) for k in ("gamma", "tau", "lr"))
+            mine = (float(self._gamma), float(self._tau), float(self.optimizer.learning_rate))
+            if (g[slot], t[slot], lr[slot]) != mine:
+                g[slot], t[slot], lr[slot] = mine
+                engine.set_learning(gamma=g, tau=t, lr=lr)
 
     def _device(self):
         if self._engine is None:
