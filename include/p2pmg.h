@@ -138,7 +138,8 @@ typedef struct p2pmg_config {
  *     never episode_fast_kernel or episode_sq16_kernel; p2pmg_set_battery, p2pmg_set_hp_levels and
  *     p2pmg_set_thermal work as with shared_q = 1.
  *   - learner = DQN: p2pmg_create returns P2PMG_E_UNSUPPORTED (p2pmg_last_error(NULL) on the calling
- *     thread says why); a Q-network per role is not built.
+ *     thread says why); a Q-network per role is not built.  (It is built another way: create with
+ *     shared_q = 1 and learner = DQN, then p2pmg_dqn_setup_roles instead of p2pmg_dqn_setup.)
  *   - memory: N tables of n_states x 4 elements (5.1 MB each in f64 at 20^4 states) and a delta
  *     buffer of 8 copies x N x 5.1 MB of int64 (2.6 GB at N = 64). */
 #define P2PMG_SHARED_ROLE 2
@@ -577,7 +578,8 @@ int p2pmg_replay_decode(const uint32_t* words, size_t n_words, size_t n_decision
 
 /* ---- DQN variant (rl.py:135-359, agent.py:301-350; BASELINE.json configs[4]) -------------
  * create with config.learner = P2PMG_LEARNER_DQN (no Q-table is allocated), then
- * p2pmg_dqn_setup.  Per agent (or ONE network with config.shared_q = 1): online and target
+ * p2pmg_dqn_setup.  Per agent (or ONE network with config.shared_q = 1, or one per ROLE with
+ * p2pmg_dqn_setup_roles, below): online and target
  * QNetwork 5->64->64->1 (Keras weight order, P2PMG_DQN_PARAMS floats), Adam state and a replay
  * ring of `capacity` transitions (s[4], a, r, ns[4]).  p2pmg_run_episode dispatches to the DQN
  * step pipeline: per timestep an act kernel (negotiation rounds with the Q-MLP, market, memory)
@@ -631,7 +633,7 @@ int p2pmg_dqn_train_batch(p2pmg_ctx* ctx, int net, const float* batch, float* lo
 /* Per-network learner constants of the DQN learner: each DQNAgent's own Trainer(gamma, tau, Adam(learning_rate))
  * (agent.py:306-311, rl.py:253-266), the first kernel's gradient clip (rl.py:329) and the comfort weight of each
  * agent's reward (agent.py:225-232).  gamma, tau, lr and clip are [n_nets] (A rows for per-agent networks, one row
- * for the shared network); penalty_weight is [A], per AGENT, in either case.  A NULL pointer leaves that field as
+ * for the shared network, N rows on a role context); penalty_weight is [A], per AGENT, in either case.  A NULL pointer leaves that field as
  * it is; all five NULL restore what p2pmg_dqn_setup filled in: every row from p2pmg_dqn_config, every weight from
  * config.penalty_weight.  The whole input is checked on the host before anything is uploaded: values must be
  * finite with 0 <= gamma <= 1, 0 <= tau <= 1, lr >= 0, clip > 0 and penalty_weight >= 0, else P2PMG_E_INVALID
@@ -736,8 +738,10 @@ int p2pmg_dqn_policy_changes(p2pmg_ctx* ctx, int which, int first, int count, in
  * network once, T_in / T_m stay on the chip between steps), on the context's own networks or on a POLICY
  * SET: M networks and a map agent -> network that the context owns on the device beside the learner's
  * online, target and Adam arrays.  No training call reads or writes the set, so one community of N trained
- * networks is evaluated over S scenarios (days) at once with the role map a -> a % N; p2pmg_create keeps
- * refusing P2PMG_SHARED_ROLE with the DQN learner (no per-role network is TRAINED).
+ * networks is evaluated over S scenarios (days) at once with the role map a -> a % N.  Per-role networks
+ * are TRAINED by a role context (p2pmg_dqn_setup_roles, on a context created with shared_q = 1), whose
+ * ONLINE / TARGET sources here read network a % N for agent a; p2pmg_create with P2PMG_SHARED_ROLE and the
+ * DQN learner is still refused, p2pmg_dqn_setup_roles is the route.
  *
  * p2pmg_dqn_set_policy_nets uploads count networks [count][P2PMG_DQN_PARAMS] and the map net_of [A], values
  * in [0, count).  The whole map is checked on the host before anything is uploaded: a value out of range is
@@ -786,8 +790,40 @@ int p2pmg_dqn_run_greedy(p2pmg_ctx* ctx, int source, int record);
 typedef int (*p2pmg_exchange_fn)(void* user, float* segments, int64_t floats_per_rank, int rank, int nranks);
 int p2pmg_dqn_set_exchange(p2pmg_ctx* ctx, p2pmg_exchange_fn fn, void* user, int rank, int nranks);
 /* the shared-network gradient layout in use: segments of this context, agents per train
- * workgroup, train workgroups per env step */
+ * workgroup, train workgroups per env step (a role context: 1, agents per workgroup, N x workgroups per role) */
 int p2pmg_dqn_grad_layout(p2pmg_ctx* ctx, int* segments, int* agents_per_block, int* blocks);
+
+/* One Q-network per ROLE: the reference's DQN community (get_community(DQNAgent, n): N DQNAgents, each with
+ * its own Trainer, network and replay buffer, agent.py:301-311) trained over S scenarios (days, weather draws,
+ * exploration streams) at once.  p2pmg_dqn_setup_roles takes the place of p2pmg_dqn_setup on a DQN context
+ * created with shared_q = 1.  The context then holds N networks (online, target, Adam m and v and one Adam
+ * iteration count each) and agent a = s N + i uses network i = a % N everywhere; replay rings, sample draws,
+ * temperatures and records stay per agent.
+ *   Errors: a tabular context, or after p2pmg_dqn_setup / p2pmg_dqn_setup_roles, P2PMG_E_STATE; a context
+ *   created with shared_q = 0, P2PMG_E_INVALID; cfg->grad_segments other than 0 or 1, P2PMG_E_INVALID; a
+ *   context that already has a communicator or a host exchange over several ranks, P2PMG_E_UNSUPPORTED.  On a
+ *   role context p2pmg_comm_init, and p2pmg_dqn_set_exchange with nranks > 1, return P2PMG_E_UNSUPPORTED:
+ *   per-role networks over several ranks or gradient segments are not built.  p2pmg_last_error gives the reason.
+ * Definition of a training env step (build-defined, like the shared network's), for every role i on its own:
+ * its agents a = k N + i, k = 0..S-1 in scenario order, are split into blocks of agents_per_block
+ * consecutive k (0: the runtime's choice, ceil(S N / (CUs x workgroups per CU)), as for the shared network).
+ * One train workgroup per block of a role chains the batch gradients of the block's agents in its
+ * registers, as the shared network's workgroups do, and writes one partial.  The role's gradient is its
+ * partials summed in dqn_reduce_adam_kernel's order (16 slices of ceil(blocks / 16) consecutive partials,
+ * each from +0.0 in order, then the slices in order) times 1.0f / (float)S; then the first kernel's clip,
+ * the Adam step at the role's own lr and iteration count and the soft update at its own tau (the
+ * expressions every other DQN context uses).  So a role context with N = 1 is the shared-network context
+ * bit for bit, and one with S = 1 the per-agent context bit for bit (one partial plus zeros, times 1).
+ * Every entry point that takes a network index or range works on [0, N): p2pmg_dqn_set_weights /
+ * get_weights, get_net_steps, dqn_forward, dqn_train_batch, the policy map calls.  p2pmg_dqn_set_learning /
+ * get_learning take gamma, tau, lr and clip as [N] rows (the comfort weight stays [A]);
+ * p2pmg_dqn_run_episode_eps works; p2pmg_dqn_run_greedy with ONLINE / TARGET evaluates agent a on network
+ * a % N, the policy set staying independent.  Episodes run dqn_act_kernel, one wave per agent
+ * (p2pmg_last_kernel: "dqn_act_kernel<N,roles>"), a train launch of N x blocks workgroups and ONE reduce + Adam
+ * launch for all N roles.
+ * p2pmg_dqn_roles: *n_roles = N on a role context, 0 on any other. */
+int p2pmg_dqn_setup_roles(p2pmg_ctx* ctx, const p2pmg_dqn_config* cfg);
+int p2pmg_dqn_roles(p2pmg_ctx* ctx, int* n_roles);
 
 /* Interleaved chains.  A chained launch (p2pmg_run_episodes) of the fast kernel may run TWO of an
  * agent's consecutive episodes per 64-lane wave, episode e in lanes 0-31 and e + 1 in lanes 32-63,

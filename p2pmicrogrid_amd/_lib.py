@@ -57,6 +57,7 @@ EXPORTS = [
     "p2pmg_sparse_count", "p2pmg_get_q_sparse", "p2pmg_set_q_sparse", "p2pmg_copy_q",
     "p2pmg_day_profile_shape", "p2pmg_day_profile",
     "p2pmg_dqn_set_policy_nets", "p2pmg_dqn_get_policy_nets", "p2pmg_dqn_run_greedy",
+    "p2pmg_dqn_setup_roles", "p2pmg_dqn_roles",
 ]
 
 
@@ -217,6 +218,8 @@ def _declare(lib):
         "p2pmg_table_hash_allgather": ([vp, vp], i32),
         "p2pmg_dqn_set_exchange": ([vp, EXCHANGE_FN, vp, i32, i32], i32),
         "p2pmg_dqn_grad_layout": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], i32),
+        "p2pmg_dqn_setup_roles": ([vp, C.POINTER(DqnConfig)], i32),
+        "p2pmg_dqn_roles": ([vp, C.POINTER(C.c_int)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

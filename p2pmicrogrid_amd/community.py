@@ -121,6 +121,10 @@ class CommunityMicrogrid:
                 eng.set_weights(w, v)
             eng.set_buffer(*carry[1])
             eng.step = carry[2]
+        elif getattr(self, "_dqn_adam", None) is not None:  # train_days ran before this engine existed
+            eng.set_weights("adam_m", self._dqn_adam[0])
+            eng.set_weights("adam_v", self._dqn_adam[1])
+            eng.step = self._dqn_adam[2]
         return eng
 
     def _ensure_engine(self) -> DeviceCommunityBatch:
@@ -439,6 +443,108 @@ class CommunityMicrogrid:
         finally:
             eng.close()
         return self._days_out(r, t_in, t_m, totals, levels, load, pv, par, profile, period)
+
+    def _role_engine(self, days):
+        """The role engine of train_days: D scenarios (the days) x N agents, shared="role", built the way
+        evaluate_days builds its batch.  Kept between calls while the days and the agents' thermal values stay
+        the same (its replay rings are then already filled); -> (engine, t_in [D, N], t_m [D, N], new)."""
+        from .dqn import DeviceDQNBatch
+        D, N = len(days), len(self.agents)
+        T = len(np.asarray(days[0]["time"]).reshape(-1))
+
+        def stack(key, shape):
+            return np.stack([np.asarray(d[key], F32).reshape(shape) for d in days])
+        time_f, t_out = stack("time", (T,)), stack("t_out", (T,))
+        load, pv = stack("load", (N, T)), stack("pv", (N, T))
+        t_in, t_m = stack("t_in", (N,)), stack("t_m", (N,))
+        max_in = np.array([F32(a.max_in) for a in self.agents], F32)
+        levels, params = thermal_arrays(self.agents)
+        capacity = int(self.agents[0].trainer.buffer.buffer_size)
+        key = (D, N, T, self._rounds, capacity) + tuple(x.tobytes() for x in (time_f, t_out, load, pv, t_in, t_m, max_in,
+                                                                           levels, params))
+        kept = getattr(self, "_role", None)
+        if kept is not None and kept[0] == key:
+            return kept[1], t_in, t_m, False
+        if kept is not None:
+            kept[1].close()
+            self._role = None
+        eng = DeviceDQNBatch(D, N, self._rounds, T, shared="role", device=self._device, capacity=capacity, init_seed=None)
+        try:
+            eng.set_env(time_f, t_out, *price_table(time_f))
+            eng.set_profiles(load, pv)
+            eng.set_max_in(np.broadcast_to(max_in, (D, N)))
+            eng.set_hp_levels(np.broadcast_to(levels, (D, N, 3)))
+            par = np.broadcast_to(params, (D, N, 4))
+            eng.set_thermal(par[..., 0], cop=par[..., 3], lower=par[..., 1], upper=par[..., 2])
+        except BaseException:
+            eng.close()
+            raise
+        self._role = (key, eng)
+        self._role_episode = 0
+        return eng, t_in, t_m, True
+
+    def train_days(self, days, episodes: int = 1, fill: Optional[int] = None) -> List[Tuple[float, float]]:
+        """Train this DQN community over several days at once: the D days are the D scenarios of ONE role
+        engine (DeviceDQNBatch(shared="role")), whose N networks are the agents' and learn from agent i of every
+        day in each env step (include/p2pmg.h, p2pmg_dqn_setup_roles), instead of D train_episode calls of one
+        scenario each.  ``days`` as for evaluate_days.  The agents' online and target networks, Adam moments and
+        iteration count are uploaded as the N role networks; on the first call for these days ``fill`` Philox
+        fill episodes (None: 5, init_buffers' count) load the engine's own replay rings, one per day and
+        agent; then ``episodes`` Philox training episodes run at the actors' current epsilon (one rate for
+        the launch: the actors' rates must be equal), every episode from the days' starting temperatures.
+        Epsilon is not decayed here: the reference's cadence (community.py main) stays with the caller.
+        Networks, Adam state and counts are written back into the agents, so evaluate_days, run, policy_maps
+        and save_to_file see the trained networks.  Returns, per training episode, (the mean over the days of
+        sum_t mean_i r, the mean loss).  Draws come from the engine's Philox streams, not np.random."""
+        if self._rule:
+            raise TypeError("train_days: a RuleAgent community has nothing to train")
+        if not self._dqn:
+            raise TypeError("train_days trains DQN communities; a tabular community trains over many days on "
+                            "DeviceCommunityBatch(shared_q=\"role\") (see run_days)")
+        if len(days) == 0 or episodes < 0:
+            raise ValueError("train_days needs at least one day and episodes >= 0")
+        eps = [float(a.actor._epsilon) for a in self.agents]
+        if len(set(eps)) != 1:
+            raise ValueError(f"train_days explores at one rate per launch; the actors' rates differ: {eps}")
+        N = len(self.agents)
+        # the Adam state: the community engine's (the trainers are bound to it) or what the last call left
+        ceng = self._engine
+        if ceng is not None:
+            steps = ceng.net_steps()
+            if len(set(int(s) for s in steps)) != 1:
+                raise NotImplementedError("train_days needs one Adam iteration count for every agent")
+            adam = (ceng.get_weights("adam_m"), ceng.get_weights("adam_v"), int(steps[0]))
+        else:
+            adam = getattr(self, "_dqn_adam", None) or (np.zeros((N, 4609), F32), np.zeros((N, 4609), F32), 0)
+        eng, t_in, t_m, new = self._role_engine(days)
+        eng.set_weights("online", np.stack([a.actor.q_network.flat_weights() for a in self.agents]))
+        eng.set_weights("target", np.stack([a.trainer.target_network.flat_weights() for a in self.agents]))
+        eng.set_weights("adam_m", adam[0])
+        eng.set_weights("adam_v", adam[1])
+        eng.step = adam[2]
+        gamma, tau, lr = dqn_learning_arrays(self.agents)
+        eng.set_learning(gamma=gamma, tau=tau, lr=lr)
+        for _ in range((5 if fill is None else int(fill)) if new else 0):
+            eng.set_temperatures(t_in, t_m)
+            eng.run_episode("fill", "philox", episode=self._role_episode, epsilon=eps[0])
+            self._role_episode += 1
+        out = []
+        for _ in range(int(episodes)):
+            eng.set_temperatures(t_in, t_m)
+            eng.run_episode("train", "philox", episode=self._role_episode, epsilon=eps[0], record=("loss",))
+            self._role_episode += 1
+            out.append((float(np.mean(eng.episode_reward(), dtype=np.float32)),
+                        float(np.mean(eng.get_record("loss"), dtype=np.float32))))
+        online, target = eng.get_weights("online"), eng.get_weights("target")
+        self._dqn_adam = (eng.get_weights("adam_m"), eng.get_weights("adam_v"), int(eng.net_steps()[0]))
+        for i, a in enumerate(self.agents):
+            a.actor.q_network.set_flat_weights(online[i])
+            a.trainer.target_network.set_flat_weights(target[i])
+        if ceng is not None:
+            ceng.set_weights("adam_m", self._dqn_adam[0])
+            ceng.set_weights("adam_v", self._dqn_adam[1])
+            ceng.step = self._dqn_adam[2]
+        return out
 
     def _run_rule(self) -> Tuple[np.ndarray, np.ndarray]:
         """run() of a RuleAgent community: one rule_episode_kernel launch (R = 0)."""

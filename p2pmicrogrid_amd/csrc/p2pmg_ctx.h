@@ -195,6 +195,10 @@ struct p2pmg_ctx : p2pmg::PlanFacts {
   bool dqn = false;
   p2pmg_dqn_config dcfg{};
   int n_nets = 0;
+  // p2pmg_dqn_setup_roles: n_nets = N networks, agent a on network a % N (d_role_map [A], what
+  // p2pmg_dqn_run_greedy hands the evaluation kernel as net_of); d_bps / d_blocks count per role / in all
+  bool dqn_roles = false;
+  DevBuf<int32_t> d_role_map;
   DevBuf<float> d_theta, d_target, d_m, d_v;  // [n_nets][kNetStride]
   DevBuf<float> d_grad;   // shared network: [d_blocks][kNetStride] partials
   DevBuf<float> d_alt;    // shared network: the other half of the Adam double buffer, [4][kNetStride]

@@ -115,7 +115,8 @@ __global__ __launch_bounds__((dqn_act_waves<NC, WIDE>() * kWave)) void dqn_act_k
     const float* w2col;
   };
   auto load_unit = [&](int a) -> Unit {
-    const float* th = d.theta + (size_t)(d.n_nets == 1 ? 0 : a) * kNetStride;
+    // the agent's network: its role's (a % N = a - s N) on a role context, the shared one, or its own
+    const float* th = d.theta + (size_t)(d.roles ? a - s * n : (d.n_nets == 1 ? 0 : a)) * kNetStride;
     return Unit{th[kOffW1 + 0 * kH + lane], th[kOffW1 + 1 * kH + lane], th[kOffW1 + 2 * kH + lane],
                 th[kOffW1 + 3 * kH + lane], th[kOffW1 + 4 * kH + lane], th[kOffB1 + lane],
                 th[kOffB2 + lane],          th[kOffW3 + lane],          th[kOffB3],

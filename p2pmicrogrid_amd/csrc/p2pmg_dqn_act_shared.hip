@@ -395,7 +395,8 @@ __global__ __launch_bounds__(256) void dqn_act_shared_kernel(const DqnParams d) 
 bool act_shared_mfma(const DqnParams& d) {
   // sizes the MFMA act kernel is built for (its action records pack 8 rounds)
   const bool mfma_n = ((d.e.N >= 1 && d.e.N <= 8) || d.e.N == 16) && d.e.R + 1 <= 8;
-  return d.n_nets == 1 && !d.act_wave && mfma_n;
+  // (a role context, N = 1 included, takes dqn_act_kernel: a wave of this kernel holds ONE network)
+  return d.n_nets == 1 && !d.roles && !d.act_wave && mfma_n;
 }
 
 bool dqn_act_fuses_adam(const DqnParams& d) { return act_shared_mfma(d) && d.n_segs >= 1 && d.n_segs <= kActAdamSegs; }

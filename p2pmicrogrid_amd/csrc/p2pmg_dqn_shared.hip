@@ -15,7 +15,12 @@ namespace {
 // in run order: a fixed order that depends only on the segment's block count, so a segment gives the
 // same sum on any rank and in any launch.  adam != 0 (one segment over every rank): the Adam step
 // on that sum in the same launch; else the sum goes to segs[seg_first + segment] for the gather.
+// ROLES (a role context, always with adam): blockIdx.y = the role.  Its d.bps partials follow the previous
+// role's in d.grad, its network is row blockIdx.y of the four state arrays, the mean is over its S agents
+// (d.inv_agents = 1 / S), and clip, tau and the step size are its own row's when the rows differ
+// (d.hyp, d.lr_net: wave-uniform scalar loads), so one launch steps all N networks.
 constexpr int kRedParams = 64, kRedSlices = 16, kRedBatch = 48;
+template <bool ROLES>
 __global__ __launch_bounds__(kRedParams * kRedSlices) void dqn_reduce_adam_kernel(const DqnParams d, int adam) {
   __shared__ float part[kRedSlices][kRedParams];
   const int j = threadIdx.x % kRedParams, sl = threadIdx.x / kRedParams;
@@ -23,13 +28,14 @@ __global__ __launch_bounds__(kRedParams * kRedSlices) void dqn_reduce_adam_kerne
   const int n_partials = d.bps;
   const int per = (n_partials + kRedSlices - 1) / kRedSlices;
   const int b0 = sl * per, b1 = min(n_partials, b0 + per);
+  const size_t ko = (ROLES ? (size_t)blockIdx.y * kNetStride : 0) + k;  // this parameter in the state arrays
   // the Adam state of this parameter, loaded ahead of the partials (one memory round trip less)
   float m0 = 0.0f, v0 = 0.0f, w0 = 0.0f, tg0 = 0.0f;
   if (sl == 0 && adam && k < kDqnParams) {
-    m0 = d.adam_m[k];
-    v0 = d.adam_v[k];
-    w0 = d.theta[k];
-    tg0 = d.target[k];
+    m0 = d.adam_m[ko];
+    v0 = d.adam_v[ko];
+    w0 = d.theta[ko];
+    tg0 = d.target[ko];
   }
   float s = 0.0f;
   if (k < kDqnParams) {
@@ -62,6 +68,18 @@ __global__ __launch_bounds__(kRedParams * kRedSlices) void dqn_reduce_adam_kerne
   for (int r = 1; r < kRedSlices; ++r) t += part[r][j];
   if (!adam) {
     d.segs[(size_t)(d.seg_first + blockIdx.y) * kNetStride + k] = t;
+    return;
+  }
+  if constexpr (ROLES) {
+    const float4 hyp = d.hyp ? d.hyp[blockIdx.y] : make_float4(d.gamma, d.tau, d.tau_c, d.clip);
+    const float lr = d.lr_net ? d.lr_net[blockIdx.y] : d.lr_t;
+    float gk = t * d.inv_agents;  // shared_grad at the role's own clip
+    if (k < kOffB1) gk = fminf(fmaxf(gk, -hyp.w), hyp.w);
+    const AdamStep a = adam_step(d, m0, v0, w0, gk, lr);
+    d.adam_m[ko] = a.m;
+    d.adam_v[ko] = a.v;
+    d.theta[ko] = a.w;
+    d.target[ko] = soft_update(hyp.y, hyp.z, tg0, a.w);
     return;
   }
   const AdamStep a = adam_step(d, m0, v0, w0, shared_grad(d, k, t), d.lr_t);
@@ -174,7 +192,7 @@ hipError_t launch_dqn_reduce_adam(const DqnParams& d, int segments, bool adam, h
   if (b4) hipLaunchKernelGGL((dqn_fold_kernel<SPT, 4>), grid, dim3(kRedParams * kRedSlices / SPT), 0, st, d);   \
   else hipLaunchKernelGGL((dqn_fold_kernel<SPT, 8>), grid, dim3(kRedParams * kRedSlices / SPT), 0, st, d);
   if (adam || spt == 1) {
-    hipLaunchKernelGGL(dqn_reduce_adam_kernel, grid, dim3(kRedParams * kRedSlices), 0, st, d, adam ? 1 : 0);
+    hipLaunchKernelGGL(dqn_reduce_adam_kernel<false>, grid, dim3(kRedParams * kRedSlices), 0, st, d, adam ? 1 : 0);
   } else if (spt == 2) {
     P2PMG_FOLD(2)
   } else if (spt == 8) {
@@ -185,6 +203,13 @@ hipError_t launch_dqn_reduce_adam(const DqnParams& d, int segments, bool adam, h
     P2PMG_FOLD(4)
   }
 #undef P2PMG_FOLD
+  return hipGetLastError();
+}
+
+hipError_t launch_dqn_reduce_adam_roles(const DqnParams& d, hipStream_t st) {
+  if (d.roles < 1 || d.bps < 1 || d.n_nets != d.roles) return hipErrorInvalidValue;
+  const dim3 grid((kDqnParams + kRedParams - 1) / kRedParams, d.roles);
+  hipLaunchKernelGGL(dqn_reduce_adam_kernel<true>, grid, dim3(kRedParams * kRedSlices), 0, st, d, 1);
   return hipGetLastError();
 }
 

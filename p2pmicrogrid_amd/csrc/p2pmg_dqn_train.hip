@@ -87,8 +87,13 @@ __device__ __forceinline__ void load_train_w(TrainW& W, const float* th, const f
 #ifndef P2PMG_TRAIN_OCC
 #define P2PMG_TRAIN_OCC 2
 #endif
-template <bool SHARED>
+// ROLES (with SHARED): one network per role (p2pmg_dqn_setup_roles).  Workgroup role * bps + j chains the
+// batch gradients of agents (j apb + ag) N + role, the role's agents in scenario order, against network
+// `role`, whose W2 operands it holds in registers as the shared form holds network 0's, and writes the
+// partial [role][j] for dqn_reduce_adam_kernel<true>.
+template <bool SHARED, bool ROLES = false>
 __global__ __launch_bounds__(256, P2PMG_TRAIN_OCC) void dqn_train_kernel(const DqnParams d) {
+  static_assert(SHARED || !ROLES, "the role form writes partials");
   __shared__ float smpb[2][kB * kTrans];  // this agent's batch and the next one's (prefetched)
   __shared__ float H1t[3 * kB][kLdsRow];
   __shared__ __attribute__((aligned(16))) float H1oT[kH][kLdsRowT];  // online layer-1 activations, unit-major
@@ -110,14 +115,17 @@ __global__ __launch_bounds__(256, P2PMG_TRAIN_OCC) void dqn_train_kernel(const D
   float gb2[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gW3[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   // this workgroup's run of agents: block j of gradient segment g covers agents g * seg_agents +
   // j * apb .. (clipped to the segment), so no block straddles two segments (p2pmg_dqn_config)
+  // (role form: seg is the role, its agents are a_step = N apart and end at scenario S - 1)
   const int seg = blockIdx.x / d.bps, sblk = blockIdx.x - seg * d.bps;
-  const int a_first = seg * d.seg_agents + sblk * d.apb;
-  const int n_ag = d.batch ? 1 : max(0, min(d.apb, (seg + 1) * d.seg_agents - a_first));
-  int net = d.batch ? d.net : 0;
+  const int a_step = ROLES ? d.roles : 1;
+  const int a_first = ROLES ? sblk * d.apb * d.roles + seg : seg * d.seg_agents + sblk * d.apb;
+  const int n_ag = ROLES ? max(0, min(d.apb, p.S - sblk * d.apb))
+                         : (d.batch ? 1 : max(0, min(d.apb, (seg + 1) * d.seg_agents - a_first)));
+  int net = ROLES ? seg : (d.batch ? d.net : 0);
   // the workgroup's network's {gamma, tau, tau_c, clip}: per-agent networks train one agent per workgroup,
   // so its row (d.hyp, when the networks' constants differ) is one scalar load from a uniform address,
   // and the four values stay SGPRs like the kernel arguments they stand in for
-  const int net_h = __builtin_amdgcn_readfirstlane(d.batch ? d.net : (SHARED ? 0 : a_first));
+  const int net_h = __builtin_amdgcn_readfirstlane(ROLES ? seg : (d.batch ? d.net : (SHARED ? 0 : a_first)));
   const float4 hyp = d.hyp ? d.hyp[net_h] : make_float4(d.gamma, d.tau, d.tau_c, d.clip);
   TrainW W;
   // one shared network: the lane's 48 W2 operands (layer 2: W2[4 kk + g4][col] of the target and
@@ -146,9 +154,9 @@ __global__ __launch_bounds__(256, P2PMG_TRAIN_OCC) void dqn_train_kernel(const D
   // loads never makes the loop wait for a global round trip
   // (unconditional loads at clamped in-range indices: a branch around them would leave a
   // loop-carried register copy that waits for every load in flight)
-  const int a_last = (int)A - 1;
+  const int a_last = ROLES ? (int)A - d.roles + seg : (int)A - 1;  // the role's last agent: the clamp stays in its run
   const int tag4 = reduce4_tag();
-  int slot_n = batch_slot(d, min(a_first + 1, a_last), threadIdx.x);
+  int slot_n = batch_slot(d, min(a_first + a_step, a_last), threadIdx.x);
   __syncthreads();
 
 #if P2PMG_TRACE
@@ -156,8 +164,8 @@ __global__ __launch_bounds__(256, P2PMG_TRAIN_OCC) void dqn_train_kernel(const D
   asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");
 #endif
   for (int ag = 0; ag < n_ag; ++ag) {
-    const int a = d.batch ? 0 : a_first + ag;
-    net = d.batch ? d.net : (SHARED ? 0 : a);
+    const int a = ROLES ? a_first + ag * a_step : (d.batch ? 0 : a_first + ag);
+    net = ROLES ? seg : (d.batch ? d.net : (SHARED ? 0 : a));
     const float* th = d.theta + (size_t)net * kNetStride;
     const float* tg = d.target + (size_t)net * kNetStride;
     if (!SHARED) load_train_w(W, th, tg, col, g4, h0);
@@ -165,8 +173,8 @@ __global__ __launch_bounds__(256, P2PMG_TRAIN_OCC) void dqn_train_kernel(const D
     // prefetch the next agent's batch into registers; it goes to the other buffer at the end
     const bool has_next = !d.batch && ag + 1 < n_ag;
     float nx0, nx1;
-    batch_part_at(d, min(a + 1, a_last), threadIdx.x, (int)min((unsigned)slot_n, (unsigned)(d.cap - 1)), nx0, nx1);
-    slot_n = batch_slot(d, min(a + 2, a_last), threadIdx.x);
+    batch_part_at(d, min(a + a_step, a_last), threadIdx.x, (int)min((unsigned)slot_n, (unsigned)(d.cap - 1)), nx0, nx1);
+    slot_n = batch_slot(d, min(a + 2 * a_step, a_last), threadIdx.x);
 
     // ---- layer 1: Z1 = X W1 + b1, 6 target + 2 online row tiles (K = 4 on MFMA, the action term
     // K = 4 as an fmaf for target tiles, a second MFMA for online tiles)
@@ -456,6 +464,14 @@ hipError_t launch_dqn_train(const DqnParams& d, int blocks, bool shared_partials
     hipLaunchKernelGGL(dqn_train_kernel<true>, dim3(blocks), dim3(256), 0, st, d);
   else
     hipLaunchKernelGGL(dqn_train_kernel<false>, dim3(blocks), dim3(256), 0, st, d);
+  return hipGetLastError();
+}
+
+hipError_t launch_dqn_train_roles(const DqnParams& d, hipStream_t st) {
+  if (d.roles < 1 || d.bps < 1 || d.apb < 1 || d.batch || d.e.A != d.e.S * d.roles ||
+      (long long)d.bps * d.apb < d.e.S)  // every scenario in a block, no agent past A
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL((dqn_train_kernel<true, true>), dim3(d.roles * d.bps), dim3(256), 0, st, d);
   return hipGetLastError();
 }
 

@@ -44,6 +44,36 @@ int validate_dqn_learning(const DqnLearn* rows, int n_nets, const float* penw, i
   return P2PMG_OK;
 }
 
+int validate_dqn_roles_world(const char* call, int nranks, bool communicator, std::string* why) {
+  if (why) why->clear();
+  if (!communicator && nranks <= 1) return P2PMG_OK;
+  if (why)
+    *why = std::string(call) + ": a role context (p2pmg_dqn_setup_roles) trains on one rank (per-role networks over "
+                               "several ranks are not built)";
+  return P2PMG_E_UNSUPPORTED;
+}
+
+int validate_dqn_roles(const p2pmg_config* cfg, const p2pmg_dqn_config* dq, bool set_up, int nranks, bool has_comm,
+                       std::string* why) {
+  if (why) why->clear();
+  auto bad = [&](int code, const char* what) {
+    if (why) *why = std::string("dqn_setup_roles: ") + what;
+    return code;
+  };
+  if (!cfg || !dq) return P2PMG_E_INVALID;
+  if (cfg->learner != P2PMG_LEARNER_DQN) return bad(P2PMG_E_STATE, "create the context with learner = P2PMG_LEARNER_DQN");
+  if (set_up) return bad(P2PMG_E_STATE, "already set up");
+  if (cfg->shared_q == 0)
+    return bad(P2PMG_E_INVALID, "create the context with shared_q = 1 (shared_q = 0 holds a network per agent: p2pmg_dqn_setup)");
+  if (dq->batch != 32) return bad(P2PMG_E_UNSUPPORTED, "batch must be 32");
+  if (dq->capacity < 32 || dq->capacity > 65535) return bad(P2PMG_E_INVALID, "capacity must be in [32, 65535]");
+  if (dq->agents_per_block < 0 || dq->grad_segments < 0) return bad(P2PMG_E_INVALID, "negative layout");
+  if (dq->grad_segments > 1)
+    return bad(P2PMG_E_INVALID, "grad_segments must be 0 or 1 (a role's gradient is one segment; segments are the "
+                                "several-rank layout, which per-role networks do not have)");
+  return validate_dqn_roles_world("dqn_setup_roles", nranks, has_comm, why);
+}
+
 }  // namespace p2pmg
 
 extern "C" {

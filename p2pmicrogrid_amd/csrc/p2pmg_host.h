@@ -26,4 +26,16 @@ struct DqnLearn {
 __attribute__((visibility("hidden"))) int validate_dqn_learning(const DqnLearn* rows, int n_nets, const float* penw,
                                                                 int n_agents, std::string* why);
 
+// What p2pmg_dqn_setup_roles checks before its first device call, from the context's config and state:
+// set_up = a DQN setup call already succeeded, nranks / has_comm = the world the context was given.
+// P2PMG_E_STATE (tabular context, or set up), P2PMG_E_INVALID (shared_q = 0, a negative layout, grad_segments
+// other than 0 or 1, batch / capacity out of range) or P2PMG_E_UNSUPPORTED (batch != 32, several ranks or a
+// communicator), with *why the reason.  Not exported.
+__attribute__((visibility("hidden"))) int validate_dqn_roles(const p2pmg_config* cfg, const p2pmg_dqn_config* dq, bool set_up,
+                                                             int nranks, bool has_comm, std::string* why);
+// A role context refuses a world of several ranks (p2pmg_comm_init, p2pmg_dqn_set_exchange with nranks > 1):
+// P2PMG_E_UNSUPPORTED with *why naming `call`; P2PMG_OK for one rank without a communicator.  Not exported.
+__attribute__((visibility("hidden"))) int validate_dqn_roles_world(const char* call, int nranks, bool communicator,
+                                                                   std::string* why);
+
 }  // namespace p2pmg

@@ -112,7 +112,8 @@ constexpr uint32_t kTagSample = 0x5EED0100u;  // + j: replay-buffer sample draws
 struct DqnParams {
   EpisodeParams e;           // simulation inputs, state, records and constants (q unused)
   int t;                     // timestep of this launch
-  int n_nets;                // A (per-agent networks, the reference) or 1 (shared, config 5)
+  int n_nets;                // A (per-agent networks, the reference), 1 (shared, config 5) or N (one per role)
+  int roles;                 // 0, or N on a role context (p2pmg_dqn_setup_roles): agent a = s N + i uses network i
   float* theta;              // [n_nets][kNetStride] online network
   float* target;             // [n_nets][kNetStride] target network
   float* adam_m;
@@ -122,7 +123,7 @@ struct DqnParams {
   int seg_first;             // global index of this context's first segment
   int n_segs;                // segments over every rank
   int seg_agents;            // agents per segment (a segment is whole scenarios)
-  int bps;                   // train workgroups per segment: ceil(seg_agents / apb)
+  int bps;                   // train workgroups per segment: ceil(seg_agents / apb); roles: per role, ceil(S / apb)
   float* buf;                // [A][cap][kTrans] replay rings
   int32_t* added;            // [A] transitions ever added
   int cap;
@@ -141,7 +142,7 @@ struct DqnParams {
   const float4* hyp;
   const float* penw;         // [A] per-agent comfort weight of the reward (p2pmg_dqn_set_learning)
   const float* lr_net;       // per-agent networks whose Adam step counts differ: [n_nets] step sizes (else null: lr_t)
-  float inv_agents;          // shared: 1 / (agents over all ranks)
+  float inv_agents;          // shared: 1 / (agents over all ranks); roles: 1 / S (a role's agents)
   int apb;                   // agents per train workgroup
   const float* batch;        // explicit [32][kTrans] batch (p2pmg_dqn_train_batch) or null
   int net;                   // network of the explicit batch
@@ -162,10 +163,17 @@ hipError_t launch_dqn_sample(const DqnParams& p, hipStream_t stream);
 // (the replay-mode sample layout), from the episode-start counts d.added
 hipError_t launch_dqn_sample_prepass(const DqnParams& p, uint16_t* out, hipStream_t stream);
 hipError_t launch_dqn_train(const DqnParams& p, int blocks, bool shared_partials, hipStream_t stream);
+// the role form (p.roles = N networks): workgroup role * p.bps + j chains agents (j apb + ag) N + role,
+// ag < apb, of scenarios below S, and writes partial [role][j]; blocks = N * p.bps
+hipError_t launch_dqn_train_roles(const DqnParams& p, hipStream_t stream);
 int dqn_train_blocks_per_cu();  // train workgroups resident per CU (the build's occupancy target)
 // each local segment's sum of its train-workgroup partials -> segs[seg_first + j] (segments = local
 // segment count); adam (one segment over every rank): the Adam step on it directly
 hipError_t launch_dqn_reduce_adam(const DqnParams& p, int segments, bool adam, hipStream_t stream);
+// one launch for the p.roles networks of a role context: role i's p.bps partials in the reduce kernel's
+// order, times p.inv_agents, clip, Adam at its own step size (p.lr_net[i], else p.lr_t) and soft update
+// at its own row (p.hyp[i], else the scalars), on network i of theta / target / adam_m / adam_v
+hipError_t launch_dqn_reduce_adam_roles(const DqnParams& p, hipStream_t stream);
 // sum of the n_segs segments in global order, then mean, clip, Adam, soft update
 hipError_t launch_dqn_adam_shared(const DqnParams& p, hipStream_t stream);
 // segments the act kernel's fused Adam step sums (more take the standalone launch)

@@ -66,6 +66,10 @@ int p2pmg_comm_unique_id(uint8_t id[128]) {
 
 int p2pmg_comm_init(p2pmg_ctx* c, const uint8_t id[128], int rank, int nranks) {
   if (!c || !id || rank < 0 || nranks <= 0 || rank >= nranks) return P2PMG_E_INVALID;
+  if (c->dqn_roles) {
+    std::string why;
+    return fail(c, p2pmg::validate_dqn_roles_world("comm_init", nranks, true, &why), why);
+  }
   Rccl* r = rccl();
   if (!r) return fail(c, P2PMG_E_UNSUPPORTED, "RCCL (librccl.so) not found");
   HIP_TRY(c, hipSetDevice(c->device));
@@ -171,6 +175,10 @@ int p2pmg_dqn_set_exchange(p2pmg_ctx* c, p2pmg_exchange_fn fn, void* user, int r
     return P2PMG_OK;
   }
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(c, P2PMG_E_INVALID, "dqn_set_exchange: rank / nranks");
+  if (c->dqn_roles && nranks > 1) {
+    std::string why;
+    return fail(c, p2pmg::validate_dqn_roles_world("dqn_set_exchange", nranks, false, &why), why);
+  }
   c->xfn = fn;
   c->xuser = user;
   c->rank = rank;

@@ -75,7 +75,9 @@ p2pmg::DqnParams dqn_params(p2pmg_ctx* c, const EpisodeParams& e) {
   d.clip = (float)r0.clip;
   d.hyp = c->d_hyp_mixed ? c->d_hyp.get() : nullptr;
   d.penw = c->d_penw;
-  d.inv_agents = 1.0f / (float)((double)c->A * c->nranks);
+  d.roles = c->dqn_roles ? c->N : 0;
+  // the mean's divisor: every agent of every rank for the shared network, a role's S agents on a role context
+  d.inv_agents = 1.0f / (float)(c->dqn_roles ? (double)c->S : (double)c->A * c->nranks);
   d.apb = c->d_apb;
   d.theta_out = d.theta;  // the Adam steps store in place unless the episode loop binds the double buffer
   d.target_out = d.target;
@@ -182,7 +184,10 @@ int dqn_train_step(p2pmg_ctx* c, p2pmg::DqnParams& d, bool same, bool defer) {
   d.lr_t = adam_lr(c->dcfg, c->h_dlearn[0].lr, c->d_steps[0] + 1);
   d.lr_net = same ? nullptr : c->d_lr + (size_t)d.t * c->d_steps.size();
   if (!d.fused_sample) HIP_TRY(c, p2pmg::launch_dqn_sample(d, c->stream));
-  if (c->n_nets == 1) {
+  if (c->dqn_roles) {  // N networks: each role's partials, then every role's sum + Adam in one launch
+    HIP_TRY(c, p2pmg::launch_dqn_train_roles(d, c->stream));
+    HIP_TRY(c, p2pmg::launch_dqn_reduce_adam_roles(d, c->stream));
+  } else if (c->n_nets == 1) {
     HIP_TRY(c, p2pmg::launch_dqn_train(d, c->d_blocks, true, c->stream));
     if (c->nranks == 1 && c->d_seg_local == 1) {  // one segment in all: its sum + Adam in one launch
       HIP_TRY(c, p2pmg::launch_dqn_reduce_adam(d, 1, true, c->stream));
@@ -307,16 +312,17 @@ int p2pmg::rt::dqn_run_episode(p2pmg_ctx* c, const p2pmg_episode_args* args) {
   }
   RC_TRY(settle());
   RC_TRY(end_timed(c, tm, true));
-  finish_launch(c, tm, std::string(c->n_nets == 1 && !d.act_wave ? "dqn_act_shared_kernel<" : "dqn_act_kernel<") +
-                           std::to_string(c->N) + ">", args->record, 0, 0);
+  finish_launch(c, tm, std::string(c->n_nets == 1 && !c->dqn_roles && !d.act_wave ? "dqn_act_shared_kernel<" : "dqn_act_kernel<") +
+                           std::to_string(c->N) + (c->dqn_roles ? ",roles>" : ">"), args->record, 0, 0);
   if (acting) c->d_added_min += c->T;
   if (acting && args->rng == P2PMG_RNG_REPLAY) c->have_codes = c->code_src == 1;
   return P2PMG_OK;
 }
 
-extern "C" {
+namespace {
 
-int p2pmg_dqn_setup(p2pmg_ctx* c, const p2pmg_dqn_config* cfg) {
+// p2pmg_dqn_setup, and p2pmg_dqn_setup_roles (roles: N networks, every argument checked by validate_dqn_roles)
+int dqn_setup_impl(p2pmg_ctx* c, const p2pmg_dqn_config* cfg, bool roles) {
   if (!c || !cfg) return P2PMG_E_INVALID;
   if (!c->dqn) return fail(c, P2PMG_E_STATE, "dqn_setup: create the context with learner = P2PMG_LEARNER_DQN");
   if (cfg->batch != p2pmg::kDqnBatch) return fail(c, P2PMG_E_UNSUPPORTED, "dqn_setup: batch must be 32");
@@ -325,13 +331,29 @@ int p2pmg_dqn_setup(p2pmg_ctx* c, const p2pmg_dqn_config* cfg) {
   if (c->d_theta) return fail(c, P2PMG_E_STATE, "dqn_setup: already set up");
   c->dcfg = *cfg;
   const size_t A = (size_t)c->A, NS = p2pmg::kNetStride;
-  c->n_nets = c->cfg.shared_q ? 1 : c->A;
+  c->n_nets = roles ? c->N : (c->cfg.shared_q ? 1 : c->A);
   const size_t nn = (size_t)c->n_nets * NS;
   for (DevBuf<float>* b : {&c->d_theta, &c->d_target, &c->d_m, &c->d_v}) HIP_TRY(c, b->alloc(nn));
   for (DevBuf<float>* b : {&c->d_theta, &c->d_target, &c->d_m, &c->d_v})
     HIP_TRY(c, hipMemsetAsync(b->get(), 0, nn * 4, c->stream));
   if (cfg->agents_per_block < 0 || cfg->grad_segments < 0) return fail(c, P2PMG_E_INVALID, "dqn_setup: negative layout");
-  if (c->cfg.shared_q) {
+  if (roles) {
+    // per role: its S agents in blocks of apb consecutive scenarios, one partial each; N * d_bps train
+    // workgroups in all, so the automatic apb fills one wave of workgroups as the shared network's does
+    const size_t slots = (size_t)c->n_cu * (size_t)p2pmg::dqn_train_blocks_per_cu();
+    const int apb = cfg->agents_per_block > 0 ? cfg->agents_per_block : (int)((A + slots - 1) / slots);
+    c->d_apb = apb < 1 ? 1 : apb;
+    c->d_seg_local = 1;
+    c->d_seg_agents = c->A;
+    c->d_bps = (c->S + c->d_apb - 1) / c->d_apb;
+    c->d_blocks = c->N * c->d_bps;
+    HIP_TRY(c, c->d_grad.alloc((size_t)c->d_blocks * NS));
+    std::vector<int32_t> map(A);
+    for (int a = 0; a < c->A; ++a) map[(size_t)a] = a % c->N;
+    HIP_TRY(c, c->d_role_map.alloc(A));
+    RC_TRY(upload(c, {{c->d_role_map.get(), map.data(), A * sizeof(int32_t)}}));
+    c->dqn_roles = true;
+  } else if (c->cfg.shared_q) {
     // gradient segments: contiguous runs of whole scenarios; the train workgroups never straddle two
     const int G = cfg->grad_segments > 0 ? cfg->grad_segments : 1;
     if (c->S % G) return fail(c, P2PMG_E_INVALID, "dqn_setup: grad_segments must divide the scenarios");
@@ -365,6 +387,26 @@ int p2pmg_dqn_setup(p2pmg_ctx* c, const p2pmg_dqn_config* cfg) {
   c->h_dlearn.assign((size_t)c->n_nets, p2pmg::DqnLearn{cfg->gamma, cfg->tau, cfg->lr, cfg->clip});
   c->h_penw.assign(A, c->cfg.penalty_weight);
   return dqn_upload_learning(c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int p2pmg_dqn_setup(p2pmg_ctx* c, const p2pmg_dqn_config* cfg) { return dqn_setup_impl(c, cfg, false); }
+
+int p2pmg_dqn_setup_roles(p2pmg_ctx* c, const p2pmg_dqn_config* cfg) {
+  if (!c || !cfg) return P2PMG_E_INVALID;
+  std::string why;
+  const int rc = p2pmg::validate_dqn_roles(&c->cfg, cfg, c->d_theta.get() != nullptr, c->nranks, c->comm != nullptr, &why);
+  if (rc != P2PMG_OK) return fail(c, rc, why);
+  return dqn_setup_impl(c, cfg, true);
+}
+
+int p2pmg_dqn_roles(p2pmg_ctx* c, int* n_roles) {
+  if (!c || !n_roles) return P2PMG_E_INVALID;
+  *n_roles = c->dqn_roles ? c->N : 0;
+  return P2PMG_OK;
 }
 
 int p2pmg_dqn_set_learning(p2pmg_ctx* c, const double* gamma, const double* tau, const double* lr, const double* clip,

@@ -90,7 +90,7 @@ int p2pmg_dqn_run_greedy(p2pmg_ctx* c, int source, int record) {
     d.net_of = c->d_pol_map;
   } else {
     d.nets = dqn_array(c, source);
-    d.net_of = nullptr;
+    d.net_of = c->dqn_roles ? c->d_role_map.get() : nullptr;  // a role context: agent a on network a % N
     d.one_net = c->n_nets == 1 ? 1 : 0;
   }
   d.ep_acc = c->d_ep_acc;

@@ -65,20 +65,29 @@ def default_net_map(count: int, n_scenarios: int, n_agents: int) -> np.ndarray:
 class DeviceDQNBatch(DeviceCommunityBatch):
     """Device-resident batch of S communities of DQN agents.  All compute runs in libp2pmg.so."""
 
-    def __init__(self, n_scenarios: int, n_agents: int, rounds: int, horizon: int, shared: bool = False,
+    def __init__(self, n_scenarios: int, n_agents: int, rounds: int, horizon: int, shared=False,
                  device: int = 0, seed: int = 42, scenario_offset: int = 0, gamma: float = 0.95, tau: float = 0.005,
                  lr: float = 1e-5, capacity: int = 5000, agents_per_block: int = 0, grad_segments: int = 1,
                  init_seed: Optional[int] = 0, **overrides):
+        """shared: False (a network per agent of every scenario), True (one network for all) or "role": N
+        networks, agent i of every scenario on network i (p2pmg_dqn_setup_roles) -- one community of N
+        DQNAgents (agent.py:301-311) trained over S days, weather draws or exploration streams at once."""
+        role = isinstance(shared, str)
+        if role and shared != "role":
+            raise ValueError(f"shared must be False, True or 'role', got {shared!r}")
         super().__init__(n_scenarios, n_agents, rounds, horizon, q_dtype="f32", device=device, seed=seed,
-                         scenario_offset=scenario_offset, shared_q=shared, learner=_lib.LEARNER_DQN, **overrides)
+                         scenario_offset=scenario_offset, shared_q=bool(shared), learner=_lib.LEARNER_DQN, **overrides)
         dc = _lib.DqnConfig()
         _lib.check(self.L.p2pmg_dqn_config_default(C.byref(dc)), what="dqn_config_default")
         dc.gamma, dc.tau, dc.lr, dc.capacity, dc.agents_per_block = gamma, tau, lr, capacity, agents_per_block
         dc.grad_segments = grad_segments
-        self._chk(self.L.p2pmg_dqn_setup(self._ctx, C.byref(dc)), "dqn_setup")
+        if role:
+            self._chk(self.L.p2pmg_dqn_setup_roles(self._ctx, C.byref(dc)), "dqn_setup_roles")
+        else:
+            self._chk(self.L.p2pmg_dqn_setup(self._ctx, C.byref(dc)), "dqn_setup")
         self.dcfg = dc
-        self.shared = bool(shared)
-        self.n_nets = 1 if shared else self.A
+        self.shared = "role" if role else bool(shared)
+        self.n_nets = self.N if role else (1 if shared else self.A)
         self.capacity = capacity
         self._xfn = None          # the host exchange's ctypes callback (kept alive while installed)
         self._xerr = None
@@ -123,13 +132,15 @@ class DeviceDQNBatch(DeviceCommunityBatch):
 
     # ----------------------------------------------------------------- learner constants
     def _net_shape(self):
+        if self.shared == "role":
+            return (self.N,)  # one row per role's network
         return (1,) if self.shared else (self.S, self.N)
 
     def set_learning(self, gamma=None, tau=None, lr=None, clip=None, penalty_weight=None):
         """Per-network learner constants: each DQNAgent's own Trainer(gamma, tau, Adam(learning_rate))
         (agent.py:306-311) and gradient clip, and each agent's comfort weight (agent.py:225-232).  gamma,
-        tau, lr and clip: scalars or anything that broadcasts to [S, N] (per-agent networks) or [1] (the
-        shared network); penalty_weight broadcasts to [S, N] in either case.  None leaves that field as it
+        tau, lr and clip: scalars or anything that broadcasts to [S, N] (per-agent networks), [1] (the
+        shared network) or [N] (shared="role": one row per role); penalty_weight broadcasts to [S, N] in either case.  None leaves that field as it
         is; set_learning() restores the values of the constructor.  Takes effect at the next launch; the
         Adam moments and iteration counts stay (p2pmg_dqn_set_learning)."""
         def cast(x, dt, shape):
