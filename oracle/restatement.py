@@ -153,10 +153,11 @@ def seq_sum(x, axis=-1):
     return acc
 
 
-def divide_power(out, powers, N: int):
+def divide_power(out, powers, N: int, trace: Optional[dict] = None):
     """RLAgent._divide_power (agent.py:186-195), batched.
 
     out: (...,) f32; powers: (..., N) f32.  Returns (..., N) f32 row of P.
+    trace: a dict that receives the divisor `tot` and the numerators |out * |f_j|| (tests only).
     """
     out = np.asarray(out, dtype=F32)
     powers = np.asarray(powers, dtype=F32)
@@ -164,7 +165,10 @@ def divide_power(out, powers, N: int):
     filtered = np.where(keep, powers, F32(0)).astype(F32)
     tot = np.abs(seq_sum(filtered))
     even = (out * F32(1)) / F32(N)
-    prop = (out[..., None] * np.abs(filtered)) / np.where(tot == 0, F32(1), tot)[..., None]
+    num = out[..., None] * np.abs(filtered)
+    prop = num / np.where(tot == 0, F32(1), tot)[..., None]
+    if trace is not None:
+        trace["tot"], trace["num"] = tot, np.abs(num)
     return np.where((tot == 0)[..., None], even[..., None], prop).astype(F32)
 
 
@@ -205,12 +209,15 @@ def rule_assign_powers(Pv):
     return p_grid, p_p2p
 
 
-def compute_costs(g, pp, buy, inj, p2p, p: OracleParams = OracleParams()):
-    """CommunityMicrogrid._compute_costs (community.py:56-65)."""
+def compute_costs(g, pp, buy, inj, p2p, p: OracleParams = OracleParams(), trace: Optional[dict] = None):
+    """CommunityMicrogrid._compute_costs (community.py:56-65).  trace: receives the numerator of / 60."""
     g = np.asarray(g, dtype=F32)
     pp = np.asarray(pp, dtype=F32)
     c = np.where(g >= 0, g * F32(buy), g * F32(inj)).astype(F32) + pp * F32(p2p)
-    c = (c * F32(p.time_slot)) / F32(p.minutes_per_hour)
+    cnum = c * F32(p.time_slot)
+    if trace is not None:
+        trace["cost_num"] = cnum
+    c = cnum / F32(p.minutes_per_hour)
     return (c * F32(1e-3)).astype(F32)
 
 
@@ -242,9 +249,10 @@ def temperature_step(t_out, t_in, t_m, hp, p: OracleParams = OracleParams()):
 DELTA_SCALE = 2.0 ** 40  # shared-table TD deltas in int64 fixed point (build-defined)
 
 
-def battery_rule(balance, soc, cap, smin=0.1, smax=0.9, sqrt_eff=np.sqrt(0.9)):
+def battery_rule(balance, soc, cap, smin=0.1, smax=0.9, sqrt_eff=np.sqrt(0.9), trace: Optional[dict] = None):
     """RuleAgent._update_storage (agent.py:138-153) with BatteryStorage (storage.py:79-100), f64,
-    vectorised; agents with cap == 0 are untouched.  Returns (balance', soc')."""
+    vectorised; agents with cap == 0 are untouched.  Returns (balance', soc').
+    trace: receives the branch masks, the moved energy x, x / cap, the free space and both limits."""
     b = np.asarray(balance, np.float64)
     soc = np.asarray(soc, np.float64)
     cap = np.broadcast_to(np.asarray(cap, np.float64), b.shape)
@@ -258,6 +266,10 @@ def battery_rule(balance, soc, cap, smin=0.1, smax=0.9, sqrt_eff=np.sqrt(0.9)):
         xc = np.where(-energy <= avail_s, -energy, avail_s)
         soc2 = np.where(dis, soc - (xd / cap) / sqrt_eff, np.where(chg, soc + sqrt_eff * (xc / cap), soc))
         b2 = np.where(dis, b - xd / 900.0, np.where(chg, b + xc / 900.0, b))
+        if trace is not None:
+            x = np.where(dis, xd, xc)
+            trace.update(dis=dis, chg=chg, x=x, q1=x / cap, space=np.maximum(0.0, smax - soc) * cap, energy=energy,
+                         avail_energy=avail_e, avail_space=avail_s)
     return b2, soc2
 
 
@@ -383,9 +395,12 @@ class OracleBatch:
 
     def run_episode(self, mode: str = "train", codes: Optional[np.ndarray] = None,
                     rng: str = "replay", seed: int = 42, episode: int = 0, eps=0.81,
-                    agent_ids: Optional[np.ndarray] = None) -> Dict:
+                    agent_ids: Optional[np.ndarray] = None, trace: Optional[list] = None) -> Dict:
         """One episode of T steps.  mode 'train' = train_episode (community.py:149-182),
-        'greedy' = run (community.py:95-123).  Replay codes: uint8 [T, R+1, S, N]."""
+        'greedy' = run (community.py:95-123).  Replay codes: uint8 [T, R+1, S, N].
+        trace: a list that receives one dict per step with the step's intermediate values (the
+        observations before binning, and per round the net power, the p2p feature's numerator, the
+        divisor and numerators of _divide_power and the battery rule's terms); it changes no result."""
         p = self.params
         S, N, R, T = self.S, self.N, self.R, self.T
         A = S * N
@@ -423,12 +438,15 @@ class OracleBatch:
             idxs = np.zeros((R + 1, S, N, 4), dtype=np.int64)
             hp = np.zeros((S, N), dtype=F32)
             soc_r = self.soc.copy() if bat else None
+            rounds = []
             for r in range(R + 1):
+                rt = None if trace is None else {}
                 # P <- P - diag(diag(P))  community.py:76
                 d = np.arange(N)
                 P[:, d, d] = F32(0)
                 powers = -np.swapaxes(P, 1, 2)  # powers[s, i, j] = -P[s, j, i]  community.py:81
-                p2pf = (seq_sum(powers) / F32(N)) / mi  # agent.py:203
+                p2pn = seq_sum(powers) / F32(N)
+                p2pf = p2pn / mi  # agent.py:203
                 ip = state_index(p2pf, p.n_p2p, "plain")
                 row = self._row(it, iT, ib, ip)
                 qrow = self.q[tab, row]  # (S, N, 3)
@@ -446,16 +464,25 @@ class OracleBatch:
                 hp = np.take_along_axis(lv, a[..., None], axis=-1)[..., 0]
                 out = (bal * mi) + hp  # agent.py:210
                 if bat:  # battery rule on the net power, SoC committed by the final round
-                    ob_, soc_r = battery_rule(out.astype(np.float64), self.soc, cap, smin, smax, sqe)
+                    ob_, soc_r = battery_rule(out.astype(np.float64), self.soc, cap, smin, smax, sqe, trace=rt)
                     out = np.where(cap > 0, ob_.astype(F32), out).astype(F32)
-                P = divide_power(out, powers, N)  # rows stacked after all agents (Jacobi)
+                P = divide_power(out, powers, N, trace=rt)  # rows stacked after all agents (Jacobi)
+                if rt is not None:
+                    rt.update(out=out, p2p_num=p2pn, p2pf=p2pf)
+                    rounds.append(rt)
                 acts[r] = a
                 idxs[r] = np.stack([it, iT, ib, ip], axis=-1)
             if bat:
                 self.soc = soc_r
             g, pp = assign_powers(P)
-            cost = compute_costs(g, pp, buy[:, None], inj[:, None], p2pp[:, None], p)
+            st = None if trace is None else {}
+            cost = compute_costs(g, pp, buy[:, None], inj[:, None], p2pp[:, None], p, trace=st)
             rew = reward(cost, self.t_in, p)
+            if trace is not None:
+                st.update({k: np.stack([x[k] for x in rounds]) for k in rounds[0]})
+                st.update(time=np.broadcast_to(time_t[:, None], (S, N)), tnorm=tnorm, bal=bal,
+                          dt=self.t_in - F32(p.setpoint), td_delta=None)
+                trace.append(st)
             if mode == "train":
                 # QAgent.train agent.py:293-298 -> QActor.train rl.py:119-129
                 itn = state_index(np.broadcast_to(time_n[:, None], (S, N)), p.n_time, "time")
@@ -469,6 +496,8 @@ class OracleBatch:
                 if self.shared_q:
                     d = p.alpha * ((rew.astype(np.float64) + p.gamma * qmax.astype(np.float64)) - qsa.astype(np.float64))
                     np.add.at(self.q_delta, (srow.ravel(), a.ravel()), np.rint(d * DELTA_SCALE).astype(np.int64).ravel())
+                    if trace is not None:
+                        st["td_delta"] = d * DELTA_SCALE
                 elif qf is np.float64:
                     new = qsa + p.alpha * ((rew.astype(np.float64) + p.gamma * qmax) - qsa)
                 else:

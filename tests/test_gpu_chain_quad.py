@@ -88,11 +88,14 @@ def _compare(serial, key, out):
 
 
 def _oracle_chain(inp, q, n, r=R, eps=None, **cfg):
-    S, T = inp.load_w.shape[0], inp.load_w.shape[-1]
+    """inp: scenario_batch's inputs, or anything with their fields; the community size is the profiles', a
+    time table may be [T] or [S, T], and per-agent heat-pump levels are taken where inp has them."""
+    S, N, T = inp.load_w.shape
     par = OracleParams(n_time=cfg.get("n_time_states", 20), n_temp=cfg.get("n_temp_states", 20),
                        n_bal=cfg.get("n_balance_states", 20), n_p2p=cfg.get("n_p2p_states", 20))
     ob = OracleBatch(S=S, N=N, R=r, load_w=inp.load_w, pv_w=inp.pv_w, max_in=inp.max_in,
-                     env_time=np.asarray(inp.time, F32).reshape(1, -1), env_tout=inp.t_out, q_dtype=q, params=par)
+                     env_time=np.asarray(inp.time, F32).reshape(-1, T), env_tout=inp.t_out, q_dtype=q, params=par,
+                     hp_levels=getattr(inp, "hp_levels", None))
     ob.t_in, ob.t_m = inp.t_in0.copy(), inp.t_m0.copy()
     eps = _schedule(E0, n) if eps is None else eps
     sp = np.full(S * N, float(par.setpoint))
