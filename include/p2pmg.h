@@ -840,6 +840,62 @@ int p2pmg_dqn_roles(p2pmg_ctx* ctx, int* n_roles);
  * after an upload. */
 int p2pmg_chain_lag(p2pmg_ctx* ctx, int* distance, int* safe);
 
+/* Policy sets: greedy episodes that act from PACKED BYTE POLICIES, not from Q rows.  A greedy episode needs
+ * each row's greedy action and nothing else of the row; p2pmg_greedy_policy already defines that action as one
+ * byte per state (160 KB per 20^4 table against 5.12 MB in f64).  A tabular context owns, beside its tables, a
+ * POLICY SET: M packed policies [M][n_states] u8 and a map policy_of [A], agent -> policy.  No training call,
+ * p2pmg_set_q, p2pmg_zero_q, p2pmg_policy_mark or table digest reads or writes the set, and nothing here reads
+ * or writes a table (p2pmg_policy_set_capture reads tables), the policy-mark snapshot, a delta or a code buffer.
+ * All four calls: NULL context P2PMG_E_INVALID; DQN context P2PMG_E_STATE (p2pmg_dqn_set_policy_nets serves
+ * those).  A context that never calls them computes and launches exactly what it did before.
+ *
+ * Definitions, bit for bit.
+ *   rows           a policy's bytes are in p2pmg_greedy_policy's order: state (it, iT, ib, ip) at
+ *                  ((it * n_temp + iT) * n_balance + ib) * n_p2p + ip.
+ *   legal bytes    0 .. n_actions-1 and P2PMG_POLICY_UNVISITED (255).  255 ACTS AS ACTION 0, an unvisited row's
+ *                  greedy action (as p2pmg_policy_changes reads a snapshot byte).
+ *   default map    policy_of == NULL: a when M == A; a % N (role i of every scenario) when M == N; 0 when
+ *                  M == 1; tested in that order; any other M is P2PMG_E_INVALID.
+ *
+ * p2pmg_set_policy_set(count M, policies, policy_of): the whole input is checked on the host first
+ * (validate_policy_set): a byte outside the legal set, a map entry outside [0, M), M < 0, or M without a default
+ * map and policy_of == NULL give P2PMG_E_INVALID, nothing is uploaded and the set the context held stays as it
+ * was.  policies == NULL allocates M slots filled with 255.  M == 0 frees the set (the other arguments are
+ * ignored).  Memory: M * n_states + 4 * A bytes on the device; if that allocation fails, P2PMG_E_NOMEM, and the
+ * set the context held stays as it was.
+ * p2pmg_get_policy_set: *count (0: no set; nothing else is then written) and, where non-NULL, the M policies
+ * and the map in use.
+ * p2pmg_policy_set_capture(first_table, count, first_slot): slot first_slot + k becomes the packed greedy policy
+ * of table first_table + k, exactly the bytes p2pmg_greedy_policy returns for it, by the same kernel
+ * (table_digest_kernel) writing straight into the set: on the context's stream, no host round trip, no staging
+ * buffer.  Per-agent, shared and role tables, f64 and f32, any n_actions the context holds.  It does not apply a
+ * pending shared-table delta.  No set: P2PMG_E_STATE; first_table < 0, count < 0, first_table + count >
+ * n_tables, first_slot < 0 or first_slot + count > M: P2PMG_E_INVALID.  count == 0: P2PMG_OK.
+ *
+ * p2pmg_run_policy(record): ONE greedy episode of every scenario in one launch of policy_episode_kernel.  Agent
+ * a takes, in every round of every step, the action policies[policy_of[a]][state], where state is the row a
+ * greedy p2pmg_run_episode would have gathered at that point: the same time, temperature and balance bins, and
+ * the p2p bin of the round (that of p2p = 0 in round 0).  Everything else is the greedy episode of the general
+ * kernel, expression for expression: the Jacobi rounds, _divide_power, the battery rule where one is set, the
+ * pair exchange, costs, the reward at the agent's own comfort weight, the RC step at its own thermal values and
+ * heat-pump levels, sum_t mean_i r.  So with policy p the packed greedy policy of agent a's table, records,
+ * final T_in / T_m / SoC and episode rewards equal p2pmg_run_episode(P2PMG_MODE_GREEDY)'s bit for bit.  No RNG,
+ * no update.  record = a P2PMG_REC_* mask without LOSS (P2PMG_E_INVALID otherwise).  It is "the last episode
+ * launch": p2pmg_get_record, p2pmg_get_episode_reward, p2pmg_episode_summary, p2pmg_day_profile and
+ * p2pmg_last_kernel_ms work after it; p2pmg_last_kernel reads "policy_episode_kernel<N,R1=..>" (",tileNC" after
+ * N in the LDS-tile form, ",battery" with one).  Any N in 1..64 (registers for N in {1..8, 16}, LDS tiles for
+ * the rest) and any R the context accepts.  p2pmg_run_policy_ex(record, flags): flags = 0 is p2pmg_run_policy;
+ * P2PMG_FLAG_TILE_KERNEL runs the LDS-tile form at any N (the cross-check of the two forms); any other flag
+ * P2PMG_E_INVALID.
+ * Errors: no set, or before env, profiles and agent params are set, P2PMG_E_STATE; an n_actions == 2 context
+ * P2PMG_E_UNSUPPORTED, as for episodes. */
+int p2pmg_set_policy_set(p2pmg_ctx* ctx, int count, const uint8_t* policies /* [count][n_states] or NULL */,
+                         const int32_t* policy_of /* [A], values in [0, count), or NULL */);
+int p2pmg_get_policy_set(p2pmg_ctx* ctx, int* count, uint8_t* policies /* or NULL */, int32_t* policy_of /* or NULL */);
+int p2pmg_policy_set_capture(p2pmg_ctx* ctx, int first_table, int count, int first_slot);
+int p2pmg_run_policy(p2pmg_ctx* ctx, int record);
+int p2pmg_run_policy_ex(p2pmg_ctx* ctx, int record, int flags);
+
 #ifdef __cplusplus
 }
 #endif

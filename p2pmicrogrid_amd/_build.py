@@ -17,7 +17,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libp2pmg.so")
-HEADERS = ["p2pmg_internal.h", "p2pmg_device.h", "p2pmg_tabular.h", "p2pmg_fastmath.h", "p2pmg_plan.h", "p2pmg_sparse.h",
+HEADERS = ["p2pmg_internal.h", "p2pmg_device.h", "p2pmg_tabular.h", "p2pmg_episode_step.h", "p2pmg_fastmath.h", "p2pmg_plan.h", "p2pmg_sparse.h",
            "p2pmg_records.h", "p2pmg_dayprof.h",
            "p2pmg_dqn_ops.h", "p2pmg_dqn_step.h", "p2pmg_ctx.h", "p2pmg_host.h", os.path.join(ROOT, "include", "p2pmg.h")]
 ARCH = os.environ.get("P2PMG_ARCH", "gfx950")
@@ -36,6 +36,7 @@ UNITS = [
     *[("p2pmg_fast.hip", f"P2PMG_FAST_SLICE={k}", [], f"fast_{k}.o") for k in range(4)],
     ("p2pmg_sq16.hip", None, SQ16_FLAGS, "sq16.o"),
     *[("p2pmg_general.hip", f"P2PMG_GENERAL_SLICE={k}", [], f"general_{k}.o") for k in range(9)],
+    *[("p2pmg_policy.hip", f"P2PMG_POLICY_SLICE={k}", [], f"policy_{k}.o") for k in range(2)],
     *[(f"p2pmg_dqn_{u}.hip", None, [], f"p2pmg_dqn_{u}.o") for u in ("act", "act_shared", "train", "shared", "eval")],
     ("p2pmg_dqn_map.hip", None, [], "p2pmg_dqn_map.o"),
     ("p2pmg_summary.hip", None, [], "p2pmg_summary.o"),
@@ -43,7 +44,7 @@ UNITS = [
     ("p2pmg_tables.hip", None, [], "p2pmg_tables.o"),
     ("p2pmg_host.cpp", None, [], "p2pmg_host.o"),
     *[(f"p2pmg_rt_{u}.cpp", None, [], f"p2pmg_rt_{u}.o") for u in ("core", "episode", "tables", "comm", "probe", "dqn",
-                                                                     "dqn_map", "dqn_eval")],
+                                                                     "dqn_map", "dqn_eval", "policy")],
     ("p2pmg_plan.cpp", None, [], "p2pmg_plan.o"),
     ("p2pmg_sparse.cpp", None, [], "p2pmg_sparse.o"),
     ("p2pmg_dayprof.cpp", None, [], "p2pmg_dayprof_host.o"),

@@ -58,6 +58,7 @@ EXPORTS = [
     "p2pmg_day_profile_shape", "p2pmg_day_profile",
     "p2pmg_dqn_set_policy_nets", "p2pmg_dqn_get_policy_nets", "p2pmg_dqn_run_greedy",
     "p2pmg_dqn_setup_roles", "p2pmg_dqn_roles",
+    "p2pmg_set_policy_set", "p2pmg_get_policy_set", "p2pmg_policy_set_capture", "p2pmg_run_policy", "p2pmg_run_policy_ex",
 ]
 
 
@@ -220,6 +221,11 @@ def _declare(lib):
         "p2pmg_dqn_grad_layout": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], i32),
         "p2pmg_dqn_setup_roles": ([vp, C.POINTER(DqnConfig)], i32),
         "p2pmg_dqn_roles": ([vp, C.POINTER(C.c_int)], i32),
+        "p2pmg_set_policy_set": ([vp, i32, vp, vp], i32),          # count, policies [count][n_states] u8 or NULL, policy_of [A] i32 or NULL
+        "p2pmg_get_policy_set": ([vp, C.POINTER(C.c_int), vp, vp], i32),
+        "p2pmg_policy_set_capture": ([vp, i32, i32, i32], i32),    # first_table, count, first_slot
+        "p2pmg_run_policy": ([vp, i32], i32),                      # record mask
+        "p2pmg_run_policy_ex": ([vp, i32, i32], i32),              # record mask, flags (FLAG_TILE_KERNEL)
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

@@ -22,7 +22,7 @@ from . import day_profile as dayprof
 from . import dataset as ds
 from . import setup
 from .agent import ActingAgent, Agent, DQNAgent, GridAgent, QAgent, RuleAgent, agent_kind
-from .engine import DeviceCommunityBatch, price_table
+from .engine import DeviceCommunityBatch, price_table, snapshot_policy_map
 from .environment import env
 from .heating import HeatPump, HPHeating
 from .production import PV, Prosumer
@@ -443,6 +443,82 @@ class CommunityMicrogrid:
         finally:
             eng.close()
         return self._days_out(r, t_in, t_m, totals, levels, load, pv, par, profile, period)
+
+    def evaluate_policies(self, days, policies, summary: bool = False, profile: bool = False,
+                          period: Optional[int] = None):
+        """run() of this community under K packed policy snapshots over D days, all K x D (snapshot, day) pairs
+        in ONE launch of policy_episode_kernel.  ``policies``: u8 [K, N, n_states] (or [K, N, n_time, n_temp,
+        n_bal, n_p2p]), K snapshots of the community's N agents in greedy_policy's order: QActor.policy_bytes()
+        per checkpoint, ActorModel.policy_map() on the default grid per checkpoint, or a hand-written rule;
+        bytes 0..2, or 255 for action 0.  Flat bytes are read on the grid of the agents' own tables (a DQN
+        community: the default 20^4 map grid) and refused with the reason when they do not fit it; 6-D input
+        carries its grid.  ``days`` as for evaluate_days.  Scenario k * D + d is day d under
+        snapshot k, and its agent i reads policy k * N + i (engine.snapshot_policy_map).
+        Returns a list of K lists of D dicts, each what evaluate_days returns for that day when the agents hold
+        snapshot k's tables, bit for bit; ``summary=True`` adds the device summaries.  ``profile=True`` returns
+        (that, the day profile with groups = snapshot index): {"agent": {name: [K, P, N] f64}, "community":
+        {name: [K, P] f64}}, so a validation curve with its day-to-day spread comes back as K rows.
+        The engine is a ``shared_q=True`` context: ONE table, which the launch never reads, so memory is
+        K * N * n_states bytes of policies plus inputs and records, and does not grow with A * 5 MB of tables.
+        Nothing of the community changes.  The agents' thermal values, heat-pump levels and max_in are used;
+        the policies need not come from them."""
+        if self._rule:
+            raise TypeError("evaluate_policies: a RuleAgent community has no policy to replace")
+        if self._battery_rule and any(self._batteries()):
+            raise NotImplementedError("evaluate_policies does not carry battery state across days")
+        D, N = len(days), len(self.agents)
+        pol = np.asarray(policies)
+        if pol.dtype != np.uint8 or pol.ndim < 3 or pol.shape[1] != N:
+            raise ValueError(f"policies must be uint8 [K, {N}, n_states], got {pol.dtype} {pol.shape}")
+        K = int(pol.shape[0])
+        if D == 0 or K == 0:
+            return ([], None) if profile else []
+        T = len(np.asarray(days[0]["time"]).reshape(-1))
+        S = K * D
+        # the table grid the bytes were made on: the policies' own axes, else the agents' tables' (a tabular
+        # community; its actors share one shape), else the default 20^4 (a DQN community's default map grid)
+        if pol.ndim == 6:
+            grid = tuple(int(x) for x in pol.shape[2:])
+        elif pol.ndim != 3:
+            raise ValueError(f"policies must be [K, {N}, n_states] or [K, {N}, n_time, n_temp, n_bal, n_p2p], got {pol.shape}")
+        else:
+            shapes = {tuple(int(x) for x in a.actor._shape[:4]) for a in self.agents if hasattr(a.actor, "_shape")}
+            if len(shapes) > 1:
+                raise ValueError(f"evaluate_policies: the agents' tables differ in shape ({sorted(shapes)}); give the "
+                                 "policies with their grid axes")
+            grid = shapes.pop() if shapes else (20, 20, 20, 20)
+            if int(np.prod(grid)) != pol.shape[2]:
+                raise ValueError(f"evaluate_policies: flat policies of {pol.shape[2]} states do not fit the grid "
+                                 f"{grid} ({int(np.prod(grid))} states): give them as [K, {N}, n_time, n_temp, n_bal, n_p2p]")
+        dims = dict(zip(("n_time_states", "n_temp_states", "n_balance_states", "n_p2p_states"), grid))
+        pol = np.ascontiguousarray(pol.reshape(K * N, -1))
+
+        def stack(key, shape):  # [D, ...] -> [K * D, ...], day d of every snapshot
+            return np.tile(np.stack([np.asarray(d[key], F32).reshape(shape) for d in days]), (K,) + (1,) * len(shape))
+        time_f, t_out = stack("time", (T,)), stack("t_out", (T,))
+        eng = DeviceCommunityBatch(S, N, self._rounds, T, q_dtype="f32", device=self._device, shared_q=True, **dims)
+        try:
+            eng.set_policy_set(pol, policy_of=snapshot_policy_map(K, D, N))
+            eng.set_env(time_f, t_out, *price_table(time_f))
+            load, pv = stack("load", (N, T)), stack("pv", (N, T))
+            eng.set_profiles(load, pv)
+            eng.set_max_in(np.broadcast_to(np.array([F32(a.max_in) for a in self.agents], F32), (S, N)))
+            levels, params = thermal_arrays(self.agents)
+            eng.set_hp_levels(np.broadcast_to(levels, (S, N, 3)))
+            par = np.broadcast_to(params, (S, N, 4))
+            eng.set_thermal(par[..., 0], cop=par[..., 3], lower=par[..., 1], upper=par[..., 2])
+            eng.set_temperatures(stack("t_in", (N,)), stack("t_m", (N,)))
+            rec = ("grid", "p2p", "cost", "t_in", "action")
+            eng.run_policy(record=rec)
+            r = eng.get_records(rec)
+            t_in, t_m = eng.get_temperatures()
+            totals = eng.episode_summary()["agent"] if summary else None
+            prof = eng.day_profile(period=period, groups=np.repeat(np.arange(K), D), n_groups=K, as_dict=True) if profile else None
+        finally:
+            eng.close()
+        flat = self._days_out(r, t_in, t_m, totals, levels, load, pv, par, False, period)
+        out = [flat[k * D:(k + 1) * D] for k in range(K)]
+        return (out, prof) if profile else out
 
     def _role_engine(self, days):
         """The role engine of train_days: D scenarios (the days) x N agents, shared="role", built the way

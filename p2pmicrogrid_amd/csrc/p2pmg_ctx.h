@@ -161,6 +161,13 @@ struct p2pmg_ctx : p2pmg::PlanFacts {
   DevBuf<double> td_part, td_out;
   DevBuf<long long> td_cpart, td_cout;
   DevBuf<uint8_t> policy_snap;
+  // the policy set (p2pmg_set_policy_set): pset_count packed policies and the agent -> policy map, read by
+  // p2pmg_run_policy and written by p2pmg_policy_set_capture alone; no training call, table call or digest
+  // reads or writes them
+  DevBuf<uint8_t> pset;          // [pset_count][n_states]
+  DevBuf<int32_t> pset_map;      // [A]
+  std::vector<int32_t> h_pset_map;
+  int pset_count = 0;            // 0: no set
   // the sparse table checkpoints (p2pmg_get_q_sparse & co.): block counts / offsets, per-table totals and
   // bases of the last call, and the staging of one run (at most P2PMG_SPARSE_STAGE_BYTES, unless one
   // table alone holds more); all allocated on first use
@@ -322,6 +329,12 @@ RT_LOCAL int ensure_hp_on(p2pmg_ctx* c);
 
 // ---- p2pmg_rt_episode.cpp
 RT_LOCAL EpisodeParams episode_params(p2pmg_ctx* c, const p2pmg_episode_args* args);
+
+// ---- p2pmg_rt_tables.cpp
+// tables [first, first + count) as a digest call addresses them: P2PMG_OK, or the status and message of `what`
+RT_LOCAL int digest_range(p2pmg_ctx* c, int first, int count, const char* what);
+// one table_digest_kernel pass over that range with no output switched on yet
+RT_LOCAL p2pmg::TableDigestParams digest_params(p2pmg_ctx* c, int first, int count);
 
 // ---- p2pmg_rt_dqn.cpp
 RT_LOCAL int dqn_ready(p2pmg_ctx* c, const char* what);

@@ -1,6 +1,6 @@
 // p2pmg_general.hip — episode_kernel, the general tabular episode kernel: any community size up to 64
 // agents, any number of rounds, per-agent / shared / per-role tables, battery, every record.
-#include "p2pmg_tabular.h"
+#include "p2pmg_episode_step.h"
 
 namespace p2pmg {
 namespace {
@@ -14,55 +14,13 @@ namespace {
 //     issued right after that action, before the previous step's market/reward/TD work;
 //   * a TD store that hits one of those prefetched rows patches the register copy.
 // The shared-table forms sum their TD deltas in the workgroup's LDS hash (p2pmg_tabular.h).
-// The proposal matrix P of one scenario as the general kernel holds it (community.py:75-86): lane i
-// owns row i; round r reads column i of round r - 1's P (Jacobi: every agent answers the previous
-// round's proposals) and writes its new row; the market reads row i and column i of the final P.
-//   PRegs<N>  N <= 16 compiled in: row and column in registers, the column by exchange<N>
-//   PTile<NC> any community size n <= NC (16, 32, 64) at run time: the scenario's P in two LDS
-//             tiles (the round being read, the round being written) with an odd row stride, so the
-//             column read (lane i at j * stride + i) and the row read (lane i at i * stride + j) are
-//             both conflict-free.  Every agent of a scenario is a lane of the same wave, so a
-//             wavefront-scope fence orders the tiles (no workgroup barrier, no vmcnt drain).
-template <int N>
-struct PRegs {
-  float row[N], col[N];
-  float* sh;
-  int i, sl;
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int j = 0; j < N; ++j) { row[j] = 0.0f; col[j] = 0.0f; }
-  }
-  __device__ __forceinline__ void next_round() { exchange<N>(row, col, i, sl, sh); }
-  __device__ __forceinline__ float colv(int j) const { return col[j]; }
-  __device__ __forceinline__ float rowv(int j) const { return row[j]; }
-  __device__ __forceinline__ void put(int j, float v) { row[j] = v; }
-};
-template <int NC>
-struct PTile {
-  static constexpr int kStride = NC + 1;
-  static constexpr int kTile = NC * kStride;
-  float* base;  // this scenario's two tiles
-  int i, rd, wr;
-  __device__ __forceinline__ void clear() {}  // round 0 reads no column (its powers are all -0)
-  __device__ __forceinline__ void next_round() {
-    wave_lds_fence();  // every lane's row of the round just written is visible
-    rd = wr;
-    wr ^= 1;
-  }
-  __device__ __forceinline__ float colv(int j) const { return base[rd * kTile + j * kStride + i]; }
-  __device__ __forceinline__ float rowv(int j) const { return base[rd * kTile + i * kStride + j]; }
-  __device__ __forceinline__ void put(int j, float v) { base[wr * kTile + i * kStride + j] = v; }
-};
-// sum_{k < n} v_k over a scenario group of run-time size n through LDS, sequential from +0.0
-template <int NC>
-__device__ __forceinline__ float group_sum_n(float v, int i, int sl, int n, float* sh) {
-  if (i < n) sh[sl * NC + i] = v;
-  wave_lds_fence();
-  float m = 0.0f;
-  for (int k = 0; k < n; ++k) m = m + sh[sl * NC + k];
-  wave_lds_fence();
-  return m;
-}
+// The proposal matrix P of one scenario (PRegs / PTile) and the run-time group sum are
+// p2pmg_episode_step.h's, shared with policy_episode_kernel (p2pmg_policy.hip).
+// MIRROR: the step body below (a round's p2p bin, _divide_power, the market, the cost and the reward) is
+// restated, expression for expression, by that header's round_p2p_bin / divide_power / market_reward, which
+// policy_episode_kernel calls and this kernel does not.  Any edit to those expressions here must be made there
+// too (tests/test_gpu_policy_set.py compares the two kernels bit for bit after a capture).
+
 // exploration code of round r >= 8 of step t (the 64-bit code word holds rounds 0..7): the replay
 // word (r / 4) of the step, or Philox word k = t (R + 1) + r (p2pmg_device.h, oracle/philox.py)
 __device__ __forceinline__ int late_code(const EpisodeParams& p, const uint32_t* codes_a, size_t step_off, int t,

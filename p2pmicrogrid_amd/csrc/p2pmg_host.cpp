@@ -74,6 +74,45 @@ int validate_dqn_roles(const p2pmg_config* cfg, const p2pmg_dqn_config* dq, bool
   return validate_dqn_roles_world("dqn_setup_roles", nranks, has_comm, why);
 }
 
+int validate_policy_set(int count, const uint8_t* policies, const int32_t* policy_of, size_t n_states, int n_actions,
+                        int n_agents, int n_scenarios, int32_t* map_out, std::string* why) {
+  if (why) why->clear();
+  auto bad = [&](const std::string& what) {
+    if (why) *why = "set_policy_set: " + what;
+    return P2PMG_E_INVALID;
+  };
+  if (count < 1) return bad("count must be positive");
+  if (n_agents < 1 || n_scenarios < 1 || n_actions < 1 || n_actions >= P2PMG_POLICY_UNVISITED)
+    return bad("bad context shape");
+  const long long A = (long long)n_agents * n_scenarios;
+  if (policy_of) {
+    for (long long a = 0; a < A; ++a) {
+      if (policy_of[a] < 0 || policy_of[a] >= count)
+        return bad("policy_of[" + std::to_string(a) + "] = " + std::to_string(policy_of[a]) + " outside [0, " +
+                   std::to_string(count) + ")");
+      if (map_out) map_out[a] = policy_of[a];
+    }
+  } else if (count == A) {
+    for (long long a = 0; map_out && a < A; ++a) map_out[a] = (int32_t)a;
+  } else if (count == n_agents) {
+    for (long long a = 0; map_out && a < A; ++a) map_out[a] = (int32_t)(a % n_agents);  // role i of every scenario
+  } else if (count == 1) {
+    for (long long a = 0; map_out && a < A; ++a) map_out[a] = 0;
+  } else {
+    return bad("without policy_of, count must be A, N or 1");
+  }
+  if (policies) {
+    const size_t total = (size_t)count * n_states;
+    for (size_t k = 0; k < total; ++k) {
+      const uint8_t b = policies[k];
+      if (b >= n_actions && b != P2PMG_POLICY_UNVISITED)
+        return bad("byte " + std::to_string((int)b) + " at policy " + std::to_string(k / n_states) + ", state " +
+                   std::to_string(k % n_states) + " is neither an action nor P2PMG_POLICY_UNVISITED");
+    }
+  }
+  return P2PMG_OK;
+}
+
 }  // namespace p2pmg
 
 extern "C" {

@@ -2,6 +2,8 @@
 // of a config and their check.  Includes no HIP header, so a program without a GPU can check it
 // (tests/test_cpu_host_unit.py).
 #pragma once
+#include <cstddef>
+#include <cstdint>
 #include <string>
 
 #include "p2pmg.h"
@@ -37,5 +39,15 @@ __attribute__((visibility("hidden"))) int validate_dqn_roles(const p2pmg_config*
 // P2PMG_E_UNSUPPORTED with *why naming `call`; P2PMG_OK for one rank without a communicator.  Not exported.
 __attribute__((visibility("hidden"))) int validate_dqn_roles_world(const char* call, int nranks, bool communicator,
                                                                    std::string* why);
+
+// What p2pmg_set_policy_set checks before its first device call: count M >= 1 policies [M][n_states] (or null:
+// M empty slots) and the map policy_of [n_agents * n_scenarios] (or null: the default map).  Legal bytes are
+// 0 .. n_actions-1 and P2PMG_POLICY_UNVISITED; map entries lie in [0, M).  On P2PMG_OK map_out (where non-null,
+// [A]) holds the map in use: policy_of, or the default a (M == A), a % N (M == N), 0 (M == 1), tested in that
+// order.  Else P2PMG_E_INVALID with *why naming the first offending byte or entry, and map_out unspecified.
+// Not exported.
+__attribute__((visibility("hidden"))) int validate_policy_set(int count, const uint8_t* policies, const int32_t* policy_of,
+                                                              size_t n_states, int n_actions, int n_agents, int n_scenarios,
+                                                              int32_t* map_out, std::string* why);
 
 }  // namespace p2pmg

@@ -290,6 +290,18 @@ hipError_t launch_role_n1_4(const EpisodeParams& p, int q_dtype, hipStream_t str
 hipError_t launch_role_n5_8(const EpisodeParams& p, int q_dtype, hipStream_t stream);
 hipError_t launch_role_n16_tile16(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
 hipError_t launch_role_tile32_64(const EpisodeParams& p, int q_dtype, int nc, hipStream_t stream);
+// the policy episode (p2pmg_policy.hip, p2pmg_run_policy): a greedy episode whose actions are bytes of the
+// context's policy set, not argmaxes of Q rows
+struct PolicyParams {
+  EpisodeParams e;        // as for a greedy episode_kernel launch (q, qdelta, codes, eps and the seeds unused)
+  const uint8_t* pol;     // [M][n_states] packed policies: action, or 255 = action 0
+  const int32_t* pol_of;  // [A] agent -> policy, values in [0, M)
+};
+// policy_episode_kernel: registers for N in {1..8, 16}, LDS tiles for every other N <= 64 (and for any N
+// when tile != 0); one launcher per P2PMG_POLICY_SLICE behind it
+hipError_t launch_policy_episode(const PolicyParams& p, int tile, hipStream_t stream);
+hipError_t launch_policy_n1_8(const PolicyParams& p, hipStream_t stream);
+hipError_t launch_policy_n16_tiles(const PolicyParams& p, int nc, hipStream_t stream);  // nc = 0: registers, N = 16
 // RuleAgent community run (R = 0): rule_episode_kernel; hp_on [A] hysteresis state in/out
 hipError_t launch_rule_episode(const EpisodeParams& p, float* hp_on, hipStream_t stream);
 // shared table, N = 16, R <= 1 (configs[2]): episode_sq16_kernel; records packed like the fast path

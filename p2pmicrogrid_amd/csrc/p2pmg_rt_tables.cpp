@@ -17,8 +17,13 @@ int q_range_ok(p2pmg_ctx* c, int first, int count, const void* host, int dtype) 
   return dtype == P2PMG_Q_F64 || dtype == P2PMG_Q_F32;
 }
 
+}  // namespace
+
 // ---- table digests: one pass of table_digest_kernel over tables [first, first + count) with the outputs
-// of the call switched on.  Each returns `count == 0` before this is reached.
+// of the call switched on.  Each returns `count == 0` before this is reached.  (Also what
+// p2pmg_policy_set_capture, p2pmg_rt_policy.cpp, points at a policy-set slot.)
+namespace p2pmg::rt {
+
 int digest_range(p2pmg_ctx* c, int first, int count, const char* what) {
   if (!c) return P2PMG_E_INVALID;
   if (c->dqn) return fail(c, P2PMG_E_STATE, std::string(what) + ": DQN context has no Q-table");
@@ -37,6 +42,10 @@ p2pmg::TableDigestParams digest_params(p2pmg_ctx* c, int first, int count) {
   p.dword = c->n_states % 4 == 0 ? 1 : 0;  // every table's bytes then start 4-byte aligned
   return p;
 }
+
+}  // namespace p2pmg::rt
+
+namespace {
 
 // ---- sparse table checkpoints: the stored rows of tables [first, first + count) compacted on the device
 // (count, offset and scatter passes of p2pmg_tables.hip), imported by a scatter, and one table copied

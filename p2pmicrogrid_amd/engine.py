@@ -42,6 +42,28 @@ def price_table(time_f32, grid_cost_avg=cfgmod.GRID_COST_AVG, amplitude=cfgmod.G
     return buy, inj, p2p
 
 
+def default_policy_map(count: int, n_scenarios: int, n_agents: int) -> np.ndarray:
+    """The map agent -> policy of a policy set of ``count`` policies when none is given (p2pmg_set_policy_set
+    with policy_of = NULL): int32 [S * N], the identity when count == S * N, a % N (role i of every scenario)
+    when count == N, all 0 when count == 1; anything else raises.  Pure NumPy (dqn.default_net_map's twin)."""
+    A = int(n_scenarios) * int(n_agents)
+    if count == A:
+        return np.arange(A, dtype=np.int32)
+    if count == n_agents:
+        return (np.arange(A) % n_agents).astype(np.int32)
+    if count == 1:
+        return np.zeros(A, np.int32)
+    raise ValueError(f"a policy set of {count} policies needs policy_of: the default maps are for A = {A}, "
+                     f"N = {n_agents} or 1 policies")
+
+
+def snapshot_policy_map(n_snapshots: int, n_days: int, n_agents: int) -> np.ndarray:
+    """The map of CommunityMicrogrid.evaluate_policies: K snapshots x D days as S = K * D scenarios, scenario
+    k * D + d, agent i on policy k * N + i.  int32 [K * D, N]."""
+    k = np.repeat(np.arange(int(n_snapshots), dtype=np.int32), int(n_days))
+    return (k[:, None] * np.int32(n_agents) + np.arange(int(n_agents), dtype=np.int32)[None, :]).astype(np.int32)
+
+
 class DeviceCommunityBatch:
     """Device-resident batch of S communities.  All compute runs in libp2pmg.so."""
 
@@ -208,6 +230,69 @@ class DeviceCommunityBatch:
         self._chk(self.L.p2pmg_policy_changes(self._ctx, first, count, ch.ctypes.data, nv.ctypes.data,
                                               int(bool(remark))), "policy_changes")
         return {"changed": ch, "newly_visited": nv}
+
+    # ----------------------------------------------------------------- policy sets (packed byte policies)
+    def set_policy_set(self, policies=None, policy_of=None, count: Optional[int] = None):
+        """The context's policy set (p2pmg_set_policy_set): M packed policies and the map agent -> policy that
+        run_policy acts from.  policies: u8 [M, n_states] or [M, n_time, n_temp, n_bal, n_p2p] in greedy_policy's
+        order, bytes 0 .. n_actions-1 or 255 (acts as action 0); None: ``count`` empty slots (all 255), for
+        capture_policies to fill.  policy_of: int32 [S, N] or [A] with values in [0, M); None: the default
+        map (default_policy_map).  count=0 (with policies None) frees the set.  Everything is validated before
+        anything is uploaded; a refused call leaves the set as it was.  M * n_states + 4 * A bytes on the device."""
+        if policies is None:
+            if count is None:
+                raise ValueError("set_policy_set needs policies or count")
+            M, ptr = int(count), None
+        else:
+            pol = np.asarray(policies)
+            if pol.dtype != np.uint8:
+                raise ValueError(f"policies must be uint8, got {pol.dtype}")
+            if pol.ndim < 2 or pol.shape[1:] not in ((self.n_states,), tuple(self.q_shape[:-1])):
+                raise ValueError(f"policies must be [M, {self.n_states}] or [M, {', '.join(map(str, self.q_shape[:-1]))}], "
+                                 f"got {pol.shape}")
+            pol = np.ascontiguousarray(pol.reshape(pol.shape[0], self.n_states))
+            M, ptr = int(pol.shape[0]), pol.ctypes.data
+            if count is not None and int(count) != M:
+                raise ValueError(f"count = {count} but {M} policies given")
+        mp = None
+        if policy_of is not None:
+            mp = np.ascontiguousarray(np.asarray(policy_of, dtype=np.int32).reshape(-1))
+            if mp.size != self.A:
+                raise ValueError(f"policy_of must hold {self.A} entries, got {mp.size}")
+        self._chk(self.L.p2pmg_set_policy_set(self._ctx, M, ptr, None if mp is None else mp.ctypes.data), "set_policy_set")
+
+    def policy_set(self):
+        """(policies u8 [M, n_time, n_temp, n_bal, n_p2p], policy_of int32 [S, N]) as the device holds them
+        (p2pmg_get_policy_set); (None, None) without a set."""
+        n = C.c_int(0)
+        self._chk(self.L.p2pmg_get_policy_set(self._ctx, C.byref(n), None, None), "get_policy_set")
+        if n.value == 0:
+            return None, None
+        pol = np.empty((n.value, *self.q_shape[:-1]), np.uint8)
+        mp = np.empty(self.A, np.int32)
+        self._chk(self.L.p2pmg_get_policy_set(self._ctx, C.byref(n), pol.ctypes.data, mp.ctypes.data), "get_policy_set")
+        return pol, mp.reshape(self.S, self.N)
+
+    def capture_policies(self, first_table: int = 0, count: Optional[int] = None, first_slot: int = 0):
+        """Slot first_slot + k of the policy set becomes greedy_policy() of table first_table + k, on the device
+        with no host round trip (p2pmg_policy_set_capture; count None: every table from first_table on)."""
+        first_table, count = self._table_range(first_table, count)
+        self._chk(self.L.p2pmg_policy_set_capture(self._ctx, first_table, count, int(first_slot)), "policy_set_capture")
+
+    def run_policy(self, record: Sequence[str] = (), kernel: str = "auto"):
+        """One greedy episode of every scenario acting from the policy set (p2pmg_run_policy, one launch of
+        policy_episode_kernel): agent a takes policies[policy_of[a]][state] wherever a greedy run_episode would
+        take the argmax of its Q row; everything else, records included, is that episode bit for bit.
+        kernel: 'auto' | 'tile' (the LDS-tile form at any N, as in run_episode)."""
+        mask = 0
+        for r in record:
+            mask |= _lib.REC[r]
+        flags = {"auto": 0, "tile": _lib.FLAG_TILE_KERNEL}[kernel]
+        if flags:
+            self._chk(self.L.p2pmg_run_policy_ex(self._ctx, mask, flags), "run_policy")
+        else:
+            self._chk(self.L.p2pmg_run_policy(self._ctx, mask), "run_policy")
+        self._recorded = mask
 
     # ----------------------------------------------------------------- sparse table checkpoints
     def sparse_count(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:

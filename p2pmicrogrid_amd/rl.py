@@ -227,6 +227,11 @@ class QActor(ActorInterface):
             return table_digest(self.q_table)[0]
         return self._engine.greedy_policy(first=self._slot, count=1)[0]
 
+    def policy_bytes(self) -> np.ndarray:
+        """u8 [n_states]: greedy_policy() flattened in table-row order, bound or not: one policy of a policy
+        set (DeviceCommunityBatch.set_policy_set, CommunityMicrogrid.evaluate_policies)."""
+        return np.ascontiguousarray(self.greedy_policy(), np.uint8).reshape(-1)
+
     def table_stats(self) -> dict:
         """{"visited", "q_min", "q_max", "abs_max": scalars, "greedy": [n_actions] i64} of this actor's
         table (p2pmg_table_stats on the device when bound)."""
